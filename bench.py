@@ -16,6 +16,14 @@ Usage (driver contract):
 
 Secondary surface: --stage shap benchmarks the shap stage (the 2-config
 TreeSHAP pass, reference experiment.py:520-530) instead of the scores sweep.
+
+A plain run does only what the headline figure needs: set up, warm up, time
+the K steps, print the result line.  --dump-outputs DIR additionally writes
+what the last timed step returned as DIR/<name>.npy (inputs are seeded, so
+two builds can be compared output for output).  --full is reserved for
+secondary measurements (none at present: the CPU baseline lives in
+scripts/cpu_baseline.py and every other figure here is a run of its own
+selected with --stage / --n-tests / --cells).
 """
 
 import argparse
@@ -38,7 +46,16 @@ def parse_args(argv=None):
                    help="number of grid cells (216 = full sweep)")
     p.add_argument("--stage", default="scores", choices=["scores", "shap"])
     p.add_argument("--backend", default="hip", choices=["hip", "ref"])
-    return p.parse_args(argv)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs as DIR/*.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run secondary measurements (none at present)")
+    args = p.parse_args(argv)
+    if args.steps < 1:
+        p.error("--steps must be >= 1")
+    if args.warmup < 0:
+        p.error("--warmup must be >= 0")
+    return args
 
 
 def _free_port():
@@ -89,7 +106,7 @@ def main():
             torch.cuda.synchronize()
 
     stage = bench_scores if args.stage == "scores" else bench_shap
-    one_step, report = stage(args, rank, world, use_cuda)
+    one_step, report, outputs = stage(args, rank, world, use_cuda)
 
     for _ in range(args.warmup):
         result = one_step()
@@ -110,12 +127,29 @@ def main():
         elapsed = float(t.cpu().item())
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs(result))
         print(json.dumps(report(result, elapsed)), flush=True)
 
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
     return 0
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: ndarray} as out_dir/<name>.npy (float32/float64)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, arr in arrays.items():
+        arr = np.ascontiguousarray(arr)
+        if arr.dtype not in (np.float32, np.float64):
+            arr = arr.astype(np.float64)
+        total += arr.nbytes
+        assert total <= 64 << 20, "dumped outputs exceed 64 MB"
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def bench_scores(args, rank, world, use_cuda):
@@ -170,7 +204,27 @@ def bench_scores(args, rank, world, use_cuda):
             },
         }
 
-    return one_step, report
+    def outputs(result):
+        """The sweep's scores as arrays, rows = evaluated cells in grid
+        order, columns = the dataset's projects then the grid totals.
+        counts: FP, FN, TP.  prf: precision, recall, F1, with -1 where the
+        stage yields None (zero denominator).  The per-cell wall-clock
+        t_train/t_test fields are timings, not results, and are left out."""
+        import numpy as np
+
+        cells = [k for k in iter_config_keys() if k in result]
+        projects = list(result[cells[0]][2])
+        counts = np.zeros((len(cells), len(projects) + 1, 3))
+        prf = np.zeros_like(counts)
+        for ci, keys in enumerate(cells):
+            _, _, scores, scores_total = result[keys]
+            rows = [scores[proj] for proj in projects] + [scores_total]
+            for ri, row in enumerate(rows):
+                counts[ci, ri] = row[:3]
+                prf[ci, ri] = [-1.0 if v is None else v for v in row[3:6]]
+        return {"scores_counts": counts, "scores_prf": prf}
+
+    return one_step, report, outputs
 
 
 def bench_shap(args, rank, world, use_cuda):
@@ -224,7 +278,11 @@ def bench_shap(args, rank, world, use_cuda):
             },
         }
 
-    return one_step, report
+    def outputs(result):
+        """The stage's two N x F class-0 attribution arrays (shap.pkl)."""
+        return {"shap_nod": result[0], "shap_od": result[1]}
+
+    return one_step, report, outputs
 
 
 if __name__ == "__main__":

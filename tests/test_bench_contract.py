@@ -13,6 +13,8 @@ import sys
 
 import pytest
 
+from flake16_framework_amd.dataset.synthetic import make_synthetic_tests
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 REQUIRED_KEYS = {
@@ -46,6 +48,41 @@ def test_single_rank_json_contract():
     assert out["data"] == "synthetic"
     assert out["config"]["grid_cells"] == 3
     assert out["config"]["n_tests"] == 300
+
+
+@pytest.mark.timeout(600)
+def test_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs writes the last step's scores as float .npy arrays,
+    identical from run to run with the same arguments; --full is accepted
+    and leaves the result line's meaning unchanged."""
+    import numpy as np
+
+    common = ("--backend", "ref", "--cells", "1", "--n-tests", "300",
+              "--warmup", "0")
+    a = _run_bench(*common, "--steps", "1",
+                   "--dump-outputs", str(tmp_path / "a"))
+    b = _run_bench(*common, "--steps", "1", "--full",
+                   "--dump-outputs", str(tmp_path / "b"))
+    assert a["steps"] == 1 and b["steps"] == 1
+    # value and ms_per_step describe the same timed steps
+    assert a["value"] == pytest.approx(1000.0 / a["ms_per_step"])
+    assert REQUIRED_KEYS <= set(b)
+    assert a["metric"] == b["metric"] and a["unit"] == b["unit"]
+
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["scores_counts.npy", "scores_prf.npy"]
+    assert sorted(os.listdir(tmp_path / "b")) == names
+    n_proj = len(make_synthetic_tests(n_tests=300, seed=0))
+    for name in names:
+        xa = np.load(tmp_path / "a" / name)
+        xb = np.load(tmp_path / "b" / name)
+        assert xa.dtype in (np.float32, np.float64)
+        assert xa.shape == (1, n_proj + 1, 3)
+        np.testing.assert_array_equal(xa, xb)
+    counts = np.load(tmp_path / "a" / "scores_counts.npy")
+    # the totals row is the sum of the per-project rows
+    np.testing.assert_array_equal(counts[:, -1], counts[:, :-1].sum(axis=1))
+    assert counts.sum() > 0
 
 
 @pytest.mark.timeout(600)

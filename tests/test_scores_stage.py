@@ -15,6 +15,7 @@ from flake16_framework_amd.constants import FLAKY
 from flake16_framework_amd.dataset.synthetic import make_synthetic_tests
 from flake16_framework_amd.engine.scores import evaluate_cell_ref, run_scores
 
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ALL_KEYS = list(iter_config_keys())
 
 
@@ -127,7 +128,7 @@ class TestDistributedGloo:
     def _launch(self, tmp_path, n_cells, port):
         out = str(tmp_path / "dist_scores.pkl")
         script = tmp_path / "worker.py"
-        script.write_text(WORKER.format(repo="/root/repo", out=out))
+        script.write_text(WORKER.format(repo=REPO, out=out))
         env = dict(os.environ, MASTER_ADDR="127.0.0.1",
                    MASTER_PORT=str(port), TEST_N_CELLS=str(n_cells))
         procs = []
@@ -160,7 +161,7 @@ class TestDistributedGloo:
         the merged shap.pkl must equal the single-process result."""
         out = str(tmp_path / "shap.pkl")
         script = tmp_path / "shap_worker.py"
-        script.write_text(SHAP_WORKER.format(repo="/root/repo", out=out))
+        script.write_text(SHAP_WORKER.format(repo=REPO, out=out))
         env = dict(os.environ, MASTER_ADDR="127.0.0.1",
                    MASTER_PORT="29613")
         procs = []
@@ -187,7 +188,7 @@ class TestDistributedGloo:
     def test_two_rank_shard_equals_single(self, tmp_path):
         out = str(tmp_path / "dist_scores.pkl")
         script = tmp_path / "worker.py"
-        script.write_text(WORKER.format(repo="/root/repo", out=out))
+        script.write_text(WORKER.format(repo=REPO, out=out))
 
         env = dict(os.environ)
         env.setdefault("MASTER_ADDR", "127.0.0.1")
