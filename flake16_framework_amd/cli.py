@@ -13,6 +13,17 @@ GPU/synthetic extensions:
   synthetic [--n-tests N] [--seed S]   write a synthetic tests.json
   scores/shap extras: --backend {auto,hip,ref}
 
+  fit [--config nod|od] [--keys K0 K1 K2 K3 K4] [--backend B]
+      [--tests-file F] [--detector OUT] [--n-trees N]
+                             fit one configuration on tests.json and save
+                             it -> detector.npz.  nod / od are the study's
+                             two best configurations (configgrid
+                             SHAP_CONFIGS); --keys names any grid cell by
+                             its five display keys
+  detect [--detector F] [--tests-file F] [--out F] [--backend B]
+                             apply a saved detector to a tests.json ->
+                             detections.json {proj: {nodeid: [proba, pred]}}
+
 Distributed: launch via `python -m torch.distributed.run --nproc-per-node N
 experiment.py scores` — one rank per GPU over RCCL; rank 0 writes the
 artifacts.
@@ -70,6 +81,41 @@ def main(argv=None):
         from .parallel import comm
         comm.init_from_env()
         write_shap(backend=backend)
+    elif command == "fit":
+        from .configgrid import SHAP_CONFIGS
+        from .constants import DETECTOR_FILE, TESTS_FILE
+        from .engine.detector import fit_detector
+        config = _pop_flag(args, "--config", "nod")
+        if config not in ("nod", "od"):
+            raise ValueError("--config takes nod or od")
+        keys = SHAP_CONFIGS[("nod", "od").index(config)]
+        if "--keys" in args:
+            i = args.index("--keys")
+            keys = tuple(args[i + 1:i + 6])
+            if len(keys) != 5:
+                raise ValueError("--keys takes five config keys")
+            del args[i:i + 6]
+        backend = _pop_flag(args, "--backend", "auto")
+        tests_file = _pop_flag(args, "--tests-file", TESTS_FILE)
+        out = _pop_flag(args, "--detector", DETECTOR_FILE)
+        n_trees = _pop_flag(args, "--n-trees", None)
+        det = fit_detector(keys, tests_file=tests_file, backend=backend,
+                           n_trees=int(n_trees) if n_trees else None)
+        det.save(out)
+        print(f"wrote {out} ({' / '.join(det.config_keys)}, "
+              f"{det.n_trees} trees, {det.n_train} training tests)")
+    elif command == "detect":
+        from .constants import DETECTIONS_FILE, DETECTOR_FILE, TESTS_FILE
+        from .engine.detector import Detector, write_detections
+        detector_file = _pop_flag(args, "--detector", DETECTOR_FILE)
+        tests_file = _pop_flag(args, "--tests-file", TESTS_FILE)
+        out = _pop_flag(args, "--out", DETECTIONS_FILE)
+        backend = _pop_flag(args, "--backend", "auto")
+        res = write_detections(Detector.load(detector_file),
+                               tests_file=tests_file, out_file=out,
+                               backend=backend)
+        print(f"wrote {out} ({len(res['pred'])} tests, "
+              f"{int(res['pred'].sum())} predicted flaky)")
     elif command == "figures":
         offline = _pop_flag(args, "--offline", False, boolean=True)
         from .report.figures import write_figures

@@ -15,6 +15,8 @@ LOG_FILE = "log.txt"
 SHAP_FILE = "shap.pkl"
 TESTS_FILE = "tests.json"
 SCORES_FILE = "scores.pkl"
+DETECTOR_FILE = "detector.npz"
+DETECTIONS_FILE = "detections.json"
 SUBJECTS_FILE = "subjects.txt"
 REQUIREMENTS_FILE = "requirements.txt"
 

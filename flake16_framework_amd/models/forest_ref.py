@@ -271,21 +271,22 @@ def _tree_leaves(tree, codes_test):
 PREDICT_TREE_BLOCK = 10
 
 
-def predict_forest(forest, codes_test):
-    """Ensemble prediction: mean per-tree class probabilities, ties ->
-    class 0 (sklearn argmax).  fp64 accumulation is BLOCKED in groups of
-    PREDICT_TREE_BLOCK trees (sequential within a block, blocks summed in
-    ascending order) — the exact association the device predict kernel
-    uses, so predictions stay bit-identical across backends."""
+def accumulate_proba(trees, codes_test):
+    """Per-row sums (acc0, acc1) of the per-tree class probabilities.
+
+    fp64 accumulation is BLOCKED in groups of PREDICT_TREE_BLOCK trees
+    (sequential within a block, blocks summed in ascending order) — the
+    exact association the device predict / proba kernels use, so the sums
+    are bit-identical across backends."""
     codes_test = np.asarray(codes_test, dtype=np.uint8)
     m = codes_test.shape[0]
     acc0 = np.zeros(m, dtype=np.float64)
     acc1 = np.zeros(m, dtype=np.float64)
 
-    for b in range(0, len(forest.trees), PREDICT_TREE_BLOCK):
+    for b in range(0, len(trees), PREDICT_TREE_BLOCK):
         b0 = np.zeros(m, dtype=np.float64)
         b1 = np.zeros(m, dtype=np.float64)
-        for tree in forest.trees[b:b + PREDICT_TREE_BLOCK]:
+        for tree in trees[b:b + PREDICT_TREE_BLOCK]:
             leaf = _tree_leaves(tree, codes_test)
             tot = tree.count0[leaf] + tree.count1[leaf]
             b0 += tree.count0[leaf] / tot
@@ -293,4 +294,51 @@ def predict_forest(forest, codes_test):
         acc0 += b0
         acc1 += b1
 
+    return acc0, acc1
+
+
+def predict_forest(forest, codes_test):
+    """Ensemble prediction: mean per-tree class probabilities, ties ->
+    class 0 (sklearn argmax); sums associated as in accumulate_proba."""
+    acc0, acc1 = accumulate_proba(forest.trees, codes_test)
     return (acc1 > acc0).astype(np.uint8)
+
+
+def canonical_order(feature, left, right):
+    """Breadth-first node order from the root (node 0): order[new] = old.
+
+    When an internal node is visited its left child takes the next free
+    id and its right child the one after, so siblings end up adjacent.
+    Nodes not reachable from the root are dropped."""
+    order = [0]
+    i = 0
+    while i < len(order):
+        node = order[i]
+        if feature[node] != LEAF:
+            order.append(int(left[node]))
+            order.append(int(right[node]))
+        i += 1
+    return np.array(order, dtype=np.int64)
+
+
+def canonicalize_tree(tree):
+    """Tree renumbered into canonical_order.  Afterwards right == left + 1
+    at every internal node; leaves hold left = right = -1, split 0."""
+    order = canonical_order(tree.feature, tree.left, tree.right)
+    new_id = np.full(tree.n_nodes, -1, dtype=np.int64)
+    new_id[order] = np.arange(len(order))
+    feature = tree.feature[order]
+    internal = feature != LEAF
+
+    def child(old):
+        return np.where(internal, new_id[np.where(internal, old[order], 0)],
+                        -1).astype(np.int32)
+
+    return Tree(
+        feature.astype(np.int32),
+        np.where(internal, tree.split_bin[order], 0).astype(np.int32),
+        np.where(internal, tree.threshold[order], 0).astype(np.float32),
+        child(tree.left), child(tree.right),
+        tree.count0[order].astype(np.float64),
+        tree.count1[order].astype(np.float64),
+    )

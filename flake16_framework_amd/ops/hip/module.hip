@@ -13,6 +13,7 @@
 #include "knn_balance.hip"
 #include "scaler_pca.hip"
 #include "treeshap.hip"
+#include "detect.hip"
 
 #include <vector>
 #include <algorithm>
@@ -633,6 +634,94 @@ at::Tensor treeshap_paths(at::Tensor codes, at::Tensor leaf_tree,
     return phi;
 }
 
+// ---------------------------------------------------------------------------
+// saved-detector inference (detect.hip)
+// ---------------------------------------------------------------------------
+// Parameters and cuts arrive CPU-resident: they are a few KB, and the cut
+// offsets are validated here before anything indexes LDS with them.
+at::Tensor detect_encode(at::Tensor X, at::Tensor mean, at::Tensor scale,
+                         at::Tensor pca_mean, at::Tensor W, bool has_pca,
+                         at::Tensor cuts, at::Tensor cut_off, int64_t F) {
+    TORCH_CHECK(X.is_cuda() && X.dtype() == at::kDouble && X.dim() == 2 &&
+                X.size(1) == FPAD && X.is_contiguous());
+    TORCH_CHECK(F >= 1 && F <= FPAD);
+    for (const at::Tensor* p : {&mean, &scale, &pca_mean, &W})
+        TORCH_CHECK(!p->is_cuda() && p->dtype() == at::kDouble &&
+                    p->is_contiguous());
+    TORCH_CHECK(mean.numel() == FPAD && scale.numel() == FPAD &&
+                pca_mean.numel() == FPAD && W.numel() == FPAD * FPAD);
+    TORCH_CHECK(!cuts.is_cuda() && cuts.dtype() == at::kFloat &&
+                cuts.is_contiguous());
+    TORCH_CHECK(!cut_off.is_cuda() && cut_off.dtype() == at::kInt &&
+                cut_off.is_contiguous() && cut_off.numel() == FPAD + 1);
+    const int* co = cut_off.data_ptr<int>();
+    TORCH_CHECK(co[0] == 0, "detect_encode: cut offsets must start at 0");
+    for (int f = 0; f < FPAD; ++f)
+        TORCH_CHECK(co[f + 1] >= co[f] &&
+                    co[f + 1] - co[f] <= DETECT_MAX_CUTS,
+                    "detect_encode: bad cut count for feature ", f);
+    const int n_cuts = co[FPAD];
+    TORCH_CHECK(n_cuts == cuts.numel(),
+                "detect_encode: cut offsets do not cover the cut array");
+
+    const at::cuda::OptionalCUDAGuard guard(X.device());
+    const long M = X.size(0);
+    TORCH_CHECK(M < (1L << 31));
+    auto codes = at::empty({M, FPAD}, X.options().dtype(at::kByte));
+    if (M == 0) return codes;
+    auto dev = X.device();
+    auto mean_d = mean.to(dev), scale_d = scale.to(dev);
+    auto pmean_d = pca_mean.to(dev), W_d = W.to(dev);
+    auto cuts_d = cuts.to(dev), off_d = cut_off.to(dev);
+    detect_encode_kernel<<<(int)((M + DETECT_BLK - 1) / DETECT_BLK),
+                           DETECT_BLK, 0, current_stream()>>>(
+        X.data_ptr<double>(), mean_d.data_ptr<double>(),
+        scale_d.data_ptr<double>(), pmean_d.data_ptr<double>(),
+        W_d.data_ptr<double>(), has_pca ? 1 : 0,
+        n_cuts ? cuts_d.data_ptr<float>() : nullptr,
+        off_d.data_ptr<int>(), n_cuts, (int)M, (int)F,
+        codes.data_ptr<uint8_t>());
+    return codes;
+}
+
+// (acc0, acc1) per row as float64 [M, 2].  The caller guarantees a
+// well-formed packed forest (engine/detector.py validates child ids
+// before packing); shapes are checked here.
+at::Tensor forest_proba(at::Tensor codes, at::Tensor tree_off,
+                        at::Tensor nodes_packed, int64_t n_trees) {
+    TORCH_CHECK(codes.is_cuda() && codes.dtype() == at::kByte &&
+                codes.dim() == 2 && codes.size(1) == FPAD &&
+                codes.is_contiguous());
+    TORCH_CHECK(tree_off.is_cuda() && tree_off.dtype() == at::kLong &&
+                tree_off.is_contiguous() && n_trees >= 1 &&
+                tree_off.numel() == n_trees + 1);
+    TORCH_CHECK(nodes_packed.is_cuda() && nodes_packed.dtype() == at::kInt &&
+                nodes_packed.dim() == 2 && nodes_packed.size(1) == 2 &&
+                nodes_packed.is_contiguous() &&
+                nodes_packed.size(0) < (1L << 31));
+    const at::cuda::OptionalCUDAGuard guard(codes.device());
+    const long M = codes.size(0);
+    TORCH_CHECK(M < (1L << 31));
+    const int n_blocks =
+        ((int)n_trees + PREDICT_TREE_BLOCK - 1) / PREDICT_TREE_BLOCK;
+    auto acc = at::empty({M, 2}, codes.options().dtype(at::kDouble));
+    if (M == 0) return acc;
+    auto partial = at::empty({(long)n_blocks * M, 2},
+                             codes.options().dtype(at::kDouble));
+    hipStream_t s = current_stream();
+    const long total = M * n_blocks;
+    forest_proba_partial_kernel<<<
+        (int)((total + DETECT_BLK - 1) / DETECT_BLK), DETECT_BLK, 0, s>>>(
+        codes.data_ptr<uint8_t>(), tree_off.data_ptr<long>(),
+        (const int2*)nodes_packed.data_ptr<int>(), (int)M, (int)n_trees,
+        n_blocks, (double2*)partial.data_ptr<double>());
+    forest_proba_combine_kernel<<<(int)((M + DETECT_BLK - 1) / DETECT_BLK),
+                                  DETECT_BLK, 0, s>>>(
+        (const double2*)partial.data_ptr<double>(), (int)M, n_blocks,
+        (double2*)acc.data_ptr<double>());
+    return acc;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("treeshap", &treeshap, py::call_guard<py::gil_scoped_release>(),
           "Path-dependent TreeSHAP (class-0), summed over trees");
@@ -669,4 +758,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("pca_fit_transform", &pca_fit_transform_dev,
           py::call_guard<py::gil_scoped_release>(),
           "Full PCA fit_transform");
+    m.def("detect_encode", &detect_encode,
+          py::call_guard<py::gil_scoped_release>(),
+          "Saved-detector scale/PCA/bin in one pass");
+    m.def("forest_proba", &forest_proba,
+          py::call_guard<py::gil_scoped_release>(),
+          "Per-row class-probability sums over a packed forest");
 }
