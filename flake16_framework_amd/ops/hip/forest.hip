@@ -14,6 +14,13 @@
 //   <= 64            small_subtree_kernel: one 64-lane wave finishes the
 //                    subtree from register-resident samples with
 //                    ballot/popcount counting
+// Only the first tier is level-synchronous.  Mid and small subtrees are
+// terminal, so the split kernels just append them to two queues that
+// accumulate over the whole fit, each item tagged with the sample buffer
+// (sidx_a / sidx_b) its range was partitioned into; the host launches
+// mid_subtree_kernel then small_subtree_kernel once after the band is
+// exhausted (mid first: it farms its <= 64 descendants into the small
+// queue), or earlier if a queue passes its drain threshold.
 // Split selection is fp64 (file compiled -ffp-contract=off) and all
 // randomness is Philox keyed on (tag, node sample-range, draw), so trees
 // are bit-identical to the numpy reference in models/forest_ref.py no
@@ -38,7 +45,10 @@ struct WorkItem {
     int start;      // job-local sidx range [start, end)
     int end;
     int depth;
-    int hist_slot;  // precomputed-histogram slot in pool[depth&1], or -1
+    // Level-queue items: precomputed-histogram slot in pool[depth&1], or
+    // -1.  Mid/small-queue items never carry a slot (route_child), so the
+    // field holds their sample-buffer tag instead: 0 = sidx_a, 1 = sidx_b.
+    int hist_slot;
 };
 
 struct ForestDev {
@@ -57,6 +67,10 @@ struct ForestDev {
     float* __restrict__ ncnt1;
     const int* __restrict__ sidx_cur;
     int* __restrict__ sidx_nxt;
+    // Both sample-index buffers by tag: deferred mid/small items outlive
+    // the level that routed them and name their buffer explicitly.
+    int* sidx_a;
+    int* sidx_b;
     const WorkItem* __restrict__ cur;
     const int* __restrict__ cur_count;
     WorkItem* __restrict__ nxt;
@@ -80,7 +94,9 @@ struct ForestDev {
     int hist_save_min;
     // Small-subtree routing: children with n <= SMALL_N go to this queue
     // and are finished wholesale by small_subtree_kernel (one wave builds
-    // the whole subtree from register-resident samples).
+    // the whole subtree from register-resident samples).  small_count and
+    // mid_count are fixed slots that accumulate over the whole fit; the
+    // host drains and resets them (see forest_fit_impl).
     WorkItem* __restrict__ small;
     int* __restrict__ small_count;
     int small_cap;
@@ -101,16 +117,25 @@ struct ForestDev {
 
 // Three-way child routing: <=SMALL_N -> wave-subtree queue, <=MID_N ->
 // LDS-staged mid-subtree queue, else next level.  Called by one thread.
+// A split kernel partitions depth-d children into the buffer of parity
+// d & 1 (root level 0 reads sidx_a), and no later level writes inside a
+// deferred child's [start, end) — every partition stays inside the
+// splitting node's own range and a job's node ranges are disjoint — so
+// the tagged item stays valid until the host drains the queue.
 __device__ __forceinline__ void route_child(const ForestDev& a,
                                             const WorkItem& w) {
     const int n = w.end - w.start;
     if (n <= SMALL_N) {
         const int i = atomicAdd(a.small_count, 1);
-        if (i < a.small_cap) a.small[i] = w;
+        if (i < a.small_cap)
+            a.small[i] = {w.job, w.node, w.start, w.end, w.depth,
+                          w.depth & 1};
         else atomicExch(a.err_flag, 1);
     } else if (n <= MID_N && w.hist_slot < 0) {
         const int i = atomicAdd(a.mid_count, 1);
-        if (i < a.mid_cap) a.mid[i] = w;
+        if (i < a.mid_cap)
+            a.mid[i] = {w.job, w.node, w.start, w.end, w.depth,
+                        w.depth & 1};
         else atomicExch(a.err_flag, 1);
     } else {
         const int i = atomicAdd(a.nxt_count, 1);
@@ -1130,8 +1155,9 @@ struct MidFrame {
 
 // Block-serial DFS (DT / fallback) needs <= log2(MID_N)+2 entries; the
 // wave-parallel mode (4 nodes in flight, breadth-ish order) can hold the
-// whole >SMALL_N frontier of a MID_N subtree (~ MID_N/SMALL_N * 2, plus
-// slack); overflow falls back to the next-level global work queue.
+// whole >SMALL_N frontier of a MID_N subtree: live frames are disjoint
+// ranges of > SMALL_N samples inside <= MID_N samples, so at most 31 of
+// them exist at once; a full stack is a logic error and trips err_flag.
 #define MID_STACK 96
 #define WAVE_CANDS 4   // wave-parallel path: max_features <= 4 (RF / ET)
 
@@ -1407,9 +1433,9 @@ __device__ __forceinline__ void mid_wave_node(
     }
     for (int i = ls + lane; i < le; i += 64) m_idx[i] = m_idx2[i];
 
-    // Route children: > SMALL_N to the shared stack (overflow: next-level
-    // global work queue — correct, just slower); <= SMALL_N to the global
-    // small queue with final global ranges.
+    // Route children: > SMALL_N to the shared stack; <= SMALL_N to the
+    // global small queue with final global ranges and this mid item's
+    // buffer tag (the write-back lands in the mid root's buffer).
     if (lane == 0) {
         const MidFrame kids[2] = {
             {(short)ls, (short)(ls + nL), depth + 1, lid},
@@ -1424,18 +1450,13 @@ __device__ __forceinline__ void mid_wave_node(
                     stack[idx] = fr;
                 } else {
                     atomicSub(sh_count, 1);
-                    const int i2 = atomicAdd(a.nxt_count, 1);
-                    if (i2 < a.work_cap)
-                        a.nxt[i2] = {it.job, fr.node, it.start + fr.s,
-                                     it.start + fr.e, fr.depth, -1};
-                    else
-                        atomicExch(a.err_flag, 1);
+                    atomicExch(a.err_flag, 1);   // unreachable (MID_STACK)
                 }
             } else {
                 const int i2 = atomicAdd(a.small_count, 1);
                 if (i2 < a.small_cap)
                     a.small[i2] = {it.job, fr.node, it.start + fr.s,
-                                   it.start + fr.e, fr.depth, -1};
+                                   it.start + fr.e, fr.depth, it.hist_slot};
                 else
                     atomicExch(a.err_flag, 1);
             }
@@ -1445,8 +1466,7 @@ __device__ __forceinline__ void mid_wave_node(
 
 template <bool STAGED>
 __launch_bounds__(HBLK)
-__global__ void mid_subtree_kernel(ForestDev a,
-                                   const int* __restrict__ sidx_level) {
+__global__ void mid_subtree_kernel(ForestDev a) {
     __shared__ uint4 m_codes[STAGED ? MID_N : 1];   // 32 KiB staged rows
     __shared__ int m_rows[MID_N];             // 4 KiB original global rows
     __shared__ uint8_t m_lab[STAGED ? MID_N : 1];   // 2 KiB labels
@@ -1474,12 +1494,14 @@ __global__ void mid_subtree_kernel(ForestDev a,
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
-    const int n_items = *a.mid_count;
+    const int n_items = min(*a.mid_count, a.mid_cap);
 
     for (int wi = blockIdx.x; wi < n_items; wi += gridDim.x) {
         const WorkItem it = a.mid[wi];
         const int n0 = it.end - it.start;
         const long sbase = a.j_sidx_off[it.job];
+        // the item's own buffer (tag): staged from and written back to
+        int* const sidx_it = it.hist_slot ? a.sidx_b : a.sidx_a;
         const long nbase = a.j_node_off[it.job];
         const uint32_t key = (uint32_t)a.j_key[it.job];
         const int F = a.F;
@@ -1487,7 +1509,7 @@ __global__ void mid_subtree_kernel(ForestDev a,
         // Stage the subtree's samples into LDS (one gather, reused by
         // every internal level).
         for (int i = tid; i < n0; i += HBLK) {
-            const int row = sidx_level[sbase + it.start + i];
+            const int row = sidx_it[sbase + it.start + i];
             m_rows[i] = row;
             if (STAGED) {
                 m_codes[i] = *reinterpret_cast<const uint4*>(
@@ -1789,7 +1811,7 @@ __global__ void mid_subtree_kernel(ForestDev a,
                         if (i < a.small_cap)
                             a.small[i] = {it.job, fr.node,
                                           it.start + fr.s, it.start + fr.e,
-                                          fr.depth, -1};
+                                          fr.depth, it.hist_slot};
                         else
                             atomicExch(a.err_flag, 1);
                     } else if (dfs_mode) {
@@ -1797,12 +1819,7 @@ __global__ void mid_subtree_kernel(ForestDev a,
                     } else if (sh_count < MID_STACK) {
                         stack[sh_count++] = fr;
                     } else {
-                        const int i2 = atomicAdd(a.nxt_count, 1);
-                        if (i2 < a.work_cap)
-                            a.nxt[i2] = {it.job, fr.node, it.start + fr.s,
-                                         it.start + fr.e, fr.depth, -1};
-                        else
-                            atomicExch(a.err_flag, 1);
+                        atomicExch(a.err_flag, 1);   // unreachable
                     }
                 }
             }
@@ -1856,7 +1873,7 @@ __global__ void mid_subtree_kernel(ForestDev a,
             }
             __syncthreads();
             for (int i = tid; i < n0; i += HBLK)
-                a.sidx_nxt[sbase + it.start + i] = m_rows[m_idx[i]];
+                sidx_it[sbase + it.start + i] = m_rows[m_idx[i]];
             __syncthreads();
             continue;
         }
@@ -1880,7 +1897,7 @@ __global__ void mid_subtree_kernel(ForestDev a,
         // after this one) reads each farmed subtree's samples
         __syncthreads();
         for (int i = tid; i < n0; i += HBLK)
-            a.sidx_nxt[sbase + it.start + i] = m_rows[m_idx[i]];
+            sidx_it[sbase + it.start + i] = m_rows[m_idx[i]];
         __syncthreads();
     }
 }
@@ -1906,8 +1923,7 @@ struct SmallFrame {
 #define SMALL_STACK 68
 
 __launch_bounds__(HBLK)
-__global__ void small_subtree_kernel(ForestDev a,
-                                     const int* __restrict__ sidx_level) {
+__global__ void small_subtree_kernel(ForestDev a) {
     __shared__ SmallFrame stack_ws[HBLK / 64][SMALL_STACK];
     __shared__ int perm_ws[HBLK / 64][FPAD];
 
@@ -1915,12 +1931,12 @@ __global__ void small_subtree_kernel(ForestDev a,
     const int wave = threadIdx.x >> 6;
     const int waves_total = gridDim.x * (HBLK / 64);
     const int wave_id = blockIdx.x * (HBLK / 64) + wave;
-    const int n_items = *a.small_count;
+    const int n_items = min(*a.small_count, a.small_cap);
     SmallFrame* stack = stack_ws[wave];
     int* perm = perm_ws[wave];
 
     for (int wi = wave_id; wi < n_items; wi += waves_total) {
-        const WorkItem it = a.small[min(wi, a.small_cap - 1)];
+        const WorkItem it = a.small[wi];
         const int n0 = it.end - it.start;
         const long sbase = a.j_sidx_off[it.job];
         const long nbase = a.j_node_off[it.job];
@@ -1933,7 +1949,8 @@ __global__ void small_subtree_kernel(ForestDev a,
         uint32_t w[4] = {0, 0, 0, 0};
         int label = 0;
         if (lane < n0) {
-            const int row = sidx_level[sbase + it.start + lane];
+            const int row =
+                (it.hist_slot ? a.sidx_b : a.sidx_a)[sbase + it.start + lane];
             uint4 cw = *reinterpret_cast<const uint4*>(
                 a.codes + (size_t)row * FPAD);
             w[0] = cw.x; w[1] = cw.y; w[2] = cw.z; w[3] = cw.w;

@@ -17,6 +17,7 @@
 
 #include <vector>
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 
 #define CHECK_HIP(expr)                                                     \
@@ -129,19 +130,22 @@ static std::vector<at::Tensor> forest_fit_impl(
                             codes.options().dtype(at::kByte));
     auto work_b = at::empty({work_cap * (long)sizeof(WorkItem)},
                             codes.options().dtype(at::kByte));
-    // per-level counter state, one 16 B memset per level:
-    // state[parity*4 + 0] = work count, +1 = pool count, +2 = small,
-    // +3 = mid
-    auto state = at::zeros({8}, opts_i32);
+    // per-level counter state, one 8 B memset per level:
+    // state[parity*4 + 0] = work count, +1 = pool count.
+    // Fixed slots outside the parity state, accumulating over the fit:
+    // state[8] = small count, state[9] = mid count.
+    auto state = at::zeros({12}, opts_i32);
     auto err = at::zeros({1}, opts_i32);
 
-    // Small queue: disjoint <= SMALL_N subtrees; S/4 covers any
-    // non-adversarial level (err_flag guards the theoretical S bound).
+    // Small queue: disjoint <= SMALL_N subtrees, accumulated until the
+    // host drains it; S/4 covers any non-adversarial fit (the drain
+    // threshold below and err_flag guard the theoretical S bound).
     const long small_cap = S_alloc / 4 + 1024;
     auto small_q = at::empty({small_cap * (long)sizeof(WorkItem)},
                              codes.options().dtype(at::kByte));
 
-    // mid-subtree queue: disjoint ranges of > SMALL_N samples each
+    // mid-subtree queue: disjoint ranges of > SMALL_N samples each, so
+    // even a whole fit's items cannot exceed S / (SMALL_N + 1)
     const long mid_cap = S_alloc / (SMALL_N + 1) + 64;
     auto mid_q = at::empty({mid_cap * (long)sizeof(WorkItem)},
                            codes.options().dtype(at::kByte));
@@ -195,8 +199,12 @@ static std::vector<at::Tensor> forest_fit_impl(
     a.small_cap = (int)small_cap;
     a.mid = (WorkItem*)mid_q.data_ptr();
     a.mid_cap = (int)mid_cap;
+    a.sidx_a = sidx_a.data_ptr<int>();
+    a.sidx_b = sidx_b.data_ptr<int>();
     int* st = state.data_ptr<int>();
     a.pool_count = st + 1;   // kernel indexes [wp * 4]
+    a.small_count = st + 8;
+    a.mid_count = st + 9;
     // wave-parallel mid-subtree mode (per-item: jobs with
     // max_features <= WAVE_CANDS); the env var forces the block-serial
     // DFS for same-box A/B runs
@@ -211,25 +219,87 @@ static std::vector<at::Tensor> forest_fit_impl(
 
     // Adaptive level grids: the deep tail of the band (skewed-split
     // chains) has a handful of items per level, where scheduling the
-    // full 4096/2048 empty-block grids is the dominant cost; once the
+    // full 4096-block grid of empty blocks is the dominant cost; once the
     // synced queue count is tiny the next chunk launches small grids
     // (grid-stride loops keep any count correct regardless).
     int lv_grid = GRID, sub_grid = 2048;
 
+    // Drain schedule.  Mid and small items are terminal — they never feed
+    // the level queue — and their sample ranges stay valid in their tagged
+    // buffer (see route_child), so nothing forces a drain per level.  By
+    // default the level loop runs only the split kernels and the two
+    // queues accumulate; they are drained once after the band is
+    // exhausted (mid first: it farms into the small queue).  The old
+    // per-level drain paid the slowest block's whole subtree as a
+    // critical path at every level (profiles/deferred_subtree_drain.md).
+    // FLAKE16_LEVEL_DRAIN=1 keeps that schedule for same-box A/B runs and
+    // the equivalence test.
+    const bool level_drain = getenv("FLAKE16_LEVEL_DRAIN") != nullptr;
+    // Capacity safety: the accumulated counts are synced with every chunk
+    // and a queue above its threshold is drained and reset mid-band.
+    // FLAKE16_DRAIN_AT=<items> lowers both thresholds (tests: the 8M-sample
+    // workspace rounding makes the real caps unreachable at small sizes).
+    long small_drain_at = small_cap / 2, mid_drain_at = mid_cap / 2;
+    if (const char* e = getenv("FLAKE16_DRAIN_AT"))
+        small_drain_at = mid_drain_at = atol(e);
+    const bool drain_stats = getenv("FLAKE16_DRAIN_STATS") != nullptr;
+    long n_drains = 0;
+
+    auto launch_mid = [&](int grid) {
+        if (mid_staged)
+            mid_subtree_kernel<true><<<grid, HBLK, 0, stream>>>(a);
+        else
+            mid_subtree_kernel<false><<<grid, HBLK, 0, stream>>>(a);
+    };
+
+    // Drain both queues given their synced counts: one block per mid item
+    // and one wave per small item (the mid kernel farms more small items
+    // than the host has seen: allow 16 per mid item), capped at 2048
+    // blocks, beyond which the grid-stride loops take over.  Measured:
+    // uncapped per-item grids (up to 65536 blocks, balanced by the
+    // hardware dispatcher) were 3.5 % slower over the sweep than this cap
+    // (profiles/deferred_subtree_drain.md); FLAKE16_DRAIN_GRID=<blocks>
+    // overrides it for A/B runs.
+    long drain_grid = 2048;
+    if (const char* e = getenv("FLAKE16_DRAIN_GRID"))
+        drain_grid = std::max<long>(1, atol(e));
+    auto drain = [&](long n_small, long n_mid) {
+        if (n_mid > 0)
+            launch_mid((int)std::min<long>(n_mid, drain_grid));
+        if (n_mid > 0 || n_small > 0) {
+            const long waves = n_small + 16 * n_mid;
+            small_subtree_kernel<<<
+                (int)std::min<long>((waves + 3) / 4, drain_grid), HBLK, 0,
+                stream>>>(a);
+        }
+        ++n_drains;
+        if (drain_stats) {
+            int after[2];
+            CHECK_HIP(hipMemcpyAsync(after, st + 8, 8,
+                                     hipMemcpyDeviceToHost, stream));
+            CHECK_HIP(hipStreamSynchronize(stream));
+            fprintf(stderr,
+                    "forest_fit drain %ld: S=%ld mid=%ld/%ld small=%d/%ld "
+                    "(%ld before the mid drain)\n",
+                    n_drains, S, n_mid, mid_cap, after[0], small_cap,
+                    n_small);
+        }
+    };
+
     // One level's dispatches: clear next-parity counters, split kernel(s),
-    // mid- and small-subtree drains, next-level count -> pinned slot.
+    // next-level count -> pinned slot.
     auto level_ops = [&](int cur_par, int pinned_slot) {
         const int nx = cur_par ^ 1;
-        // one 16 B memset clears next-level work/pool/small/mid counts
-        CHECK_HIP(hipMemsetAsync(st + nx * 4, 0, 16, stream));
+        // one 8 B memset clears the next level's work and pool counts
+        CHECK_HIP(hipMemsetAsync(st + nx * 4, 0, 8, stream));
+        if (level_drain)
+            CHECK_HIP(hipMemsetAsync(st + 8, 0, 8, stream));
         a.sidx_cur = (cur_par == 0 ? sidx_a : sidx_b).data_ptr<int>();
         a.sidx_nxt = (cur_par == 0 ? sidx_b : sidx_a).data_ptr<int>();
         a.cur = (const WorkItem*)(cur_par == 0 ? work_a : work_b).data_ptr();
         a.nxt = (WorkItem*)(cur_par == 0 ? work_b : work_a).data_ptr();
         a.cur_count = st + cur_par * 4;
         a.nxt_count = st + nx * 4;
-        a.small_count = st + nx * 4 + 2;
-        a.mid_count = st + nx * 4 + 3;
         if (any_best) {
             if (!has_wide && getenv("FLAKE16_RF_CANDONLY")) {
                 // ablation variant: candidate-only RF histograms measured
@@ -243,71 +313,46 @@ static std::vector<at::Tensor> forest_fit_impl(
         }
         if (any_rand)
             et_split_kernel<<<lv_grid, HBLK, 0, stream>>>(a);
-        if (mid_staged)
-            mid_subtree_kernel<true><<<sub_grid, HBLK, 0, stream>>>(
-                a, a.sidx_nxt);
-        else
-            mid_subtree_kernel<false><<<sub_grid, HBLK, 0, stream>>>(
-                a, a.sidx_nxt);
-        small_subtree_kernel<<<sub_grid, HBLK, 0, stream>>>(a, a.sidx_nxt);
+        if (level_drain) {
+            launch_mid(sub_grid);
+            small_subtree_kernel<<<sub_grid, HBLK, 0, stream>>>(a);
+        }
         CHECK_HIP(hipMemcpyAsync(pinned_p + pinned_slot, st + nx * 4, 4,
                                  hipMemcpyDeviceToHost, stream));
     };
 
-    if (getenv("FLAKE16_HIPGRAPH") && stream != nullptr) {
-        // MEASURED AND REJECTED (kept for A/B): the dispatch sequence is
-        // parity-periodic with every pointer fixed, so one even+odd level
-        // pair is captured into a hipGraph and replayed — but the
-        // per-fit capture+instantiate costs more than the ~12 dispatches
-        // per pair it saves (same-box sweep 123.9 vs 127.1 configs/s),
-        // so the plain loop below is the default.  Requires a non-default
-        // stream (capture on the legacy stream is not permitted).
-        // Replaying past exhaustion is harmless — all kernels early-exit
-        // on zero counts.
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t gexec = nullptr;
-        CHECK_HIP(hipStreamBeginCapture(stream,
-                                        hipStreamCaptureModeThreadLocal));
-        level_ops(0, 0);
-        level_ops(1, 1);
-        CHECK_HIP(hipStreamEndCapture(stream, &graph));
-        CHECK_HIP(hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0));
-
-        const int PAIRS_PER_SYNC = 4;
-        long pairs = 0;
-        bool done = false;
-        while (!done) {
-            for (int p = 0; p < PAIRS_PER_SYNC; ++p)
-                CHECK_HIP(hipGraphLaunch(gexec, stream));
-            CHECK_HIP(hipStreamSynchronize(stream));
-            pairs += PAIRS_PER_SYNC;
-            done = pinned_p[0] == 0 || pinned_p[1] == 0;
-            TORCH_CHECK(pairs < 4096, "forest_fit: depth limit exceeded");
+    const int CHUNK = 8;
+    int* const pinned_q = pinned_p + CHUNK;   // [0] small, [1] mid count
+    int cur = 0;
+    long lev = 0;
+    bool done = false;
+    while (!done) {
+        for (int c = 0; c < CHUNK; ++c, ++lev) {
+            level_ops(cur, c);
+            cur ^= 1;
         }
-        CHECK_HIP(hipGraphExecDestroy(gexec));
-        CHECK_HIP(hipGraphDestroy(graph));
-    } else {
-        const int CHUNK = 8;
-        int cur = 0;
-        long lev = 0;
-        bool done = false;
-        while (!done) {
-            for (int c = 0; c < CHUNK; ++c, ++lev) {
-                level_ops(cur, c % PINSZ);
-                cur ^= 1;
-            }
-            CHECK_HIP(hipStreamSynchronize(stream));
-            for (int c = 0; c < CHUNK; ++c)
-                if (pinned_p[c] == 0) { done = true; break; }
-            // shrink the next chunk's grids when the band has thinned
-            // (items can at most double per level: 16 items now bound
-            // the whole next chunk well under a 512-block grid)
-            const int last_cnt = pinned_p[CHUNK - 1];
-            lv_grid = last_cnt <= 16 ? 512 : GRID;
-            sub_grid = last_cnt <= 16 ? 512 : 2048;
-            TORCH_CHECK(lev < 8192, "forest_fit: depth limit exceeded");
+        if (!level_drain)
+            CHECK_HIP(hipMemcpyAsync(pinned_q, st + 8, 8,
+                                     hipMemcpyDeviceToHost, stream));
+        CHECK_HIP(hipStreamSynchronize(stream));
+        for (int c = 0; c < CHUNK; ++c)
+            if (pinned_p[c] == 0) { done = true; break; }
+        // shrink the next chunk's grids when the band has thinned
+        // (items can at most double per level: 16 items now bound
+        // the whole next chunk well under a 512-block grid)
+        const int last_cnt = pinned_p[CHUNK - 1];
+        lv_grid = last_cnt <= 16 ? 512 : GRID;
+        sub_grid = last_cnt <= 16 ? 512 : 2048;
+        TORCH_CHECK(lev < 8192, "forest_fit: depth limit exceeded");
+        if (!level_drain && !done &&
+            (pinned_q[0] > small_drain_at || pinned_q[1] > mid_drain_at)) {
+            drain(pinned_q[0], pinned_q[1]);
+            CHECK_HIP(hipMemsetAsync(st + 8, 0, 8, stream));
         }
     }
+    // band exhausted: the one drain of everything deferred
+    if (!level_drain)
+        drain(pinned_q[0], pinned_q[1]);
 
     TORCH_CHECK(err.to(at::kCPU).item<int>() == 0,
                 "forest_fit: work-queue capacity exceeded");
