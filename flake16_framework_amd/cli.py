@@ -23,6 +23,13 @@ GPU/synthetic extensions:
   detect [--detector F] [--tests-file F] [--out F] [--backend B]
                              apply a saved detector to a tests.json ->
                              detections.json {proj: {nodeid: [proba, pred]}}
+  explain [--detector F] [--tests-file F] [--out F] [--backend B]
+                             detect plus TreeSHAP: split every test's
+                             flaky-class probability into one contribution
+                             per model input -> explanations.json
+                             {"feature_names", "base_value", "tests":
+                             {proj: {nodeid: [proba, pred, phi...]}}};
+                             class-1 values, the negation of shap.pkl's
 
 Distributed: launch via `python -m torch.distributed.run --nproc-per-node N
 experiment.py scores` — one rank per GPU over RCCL; rank 0 writes the
@@ -116,6 +123,23 @@ def main(argv=None):
                                backend=backend)
         print(f"wrote {out} ({len(res['pred'])} tests, "
               f"{int(res['pred'].sum())} predicted flaky)")
+    elif command == "explain":
+        import numpy as np
+        from .constants import DETECTOR_FILE, EXPLANATIONS_FILE, TESTS_FILE
+        from .engine.detector import Detector
+        from .engine.explain import write_explanations
+        detector_file = _pop_flag(args, "--detector", DETECTOR_FILE)
+        tests_file = _pop_flag(args, "--tests-file", TESTS_FILE)
+        out = _pop_flag(args, "--out", EXPLANATIONS_FILE)
+        backend = _pop_flag(args, "--backend", "auto")
+        res = write_explanations(Detector.load(detector_file),
+                                 tests_file=tests_file, out_file=out,
+                                 backend=backend)
+        weight = np.abs(res["phi"]).sum(axis=0) / max(1, len(res["phi"]))
+        top = ", ".join(f"{res['feature_names'][f]} {weight[f]:.4f}"
+                        for f in np.argsort(-weight, kind="stable")[:3])
+        print(f"wrote {out} ({len(res['pred'])} tests; "
+              f"largest mean |phi|: {top})")
     elif command == "figures":
         offline = _pop_flag(args, "--offline", False, boolean=True)
         from .report.figures import write_figures

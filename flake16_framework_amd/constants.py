@@ -17,6 +17,7 @@ TESTS_FILE = "tests.json"
 SCORES_FILE = "scores.pkl"
 DETECTOR_FILE = "detector.npz"
 DETECTIONS_FILE = "detections.json"
+EXPLANATIONS_FILE = "explanations.json"
 SUBJECTS_FILE = "subjects.txt"
 REQUIREMENTS_FILE = "requirements.txt"
 

@@ -14,6 +14,7 @@
 #include "scaler_pca.hip"
 #include "treeshap.hip"
 #include "detect.hip"
+#include "explain.hip"
 
 #include <vector>
 #include <algorithm>
@@ -767,6 +768,79 @@ at::Tensor forest_proba(at::Tensor codes, at::Tensor tree_off,
     return acc;
 }
 
+// ---------------------------------------------------------------------------
+// saved-detector TreeSHAP (explain.hip)
+// ---------------------------------------------------------------------------
+// Class-1 attributions as float64 [M, FPAD] (columns >= F are zero) from
+// the codes of detect_encode and the merged-path table of
+// models/mergedpaths.py, all device-resident.  Everything the kernel
+// indexes with is checked here, on the device, with one readback.
+at::Tensor detector_shap(at::Tensor codes, at::Tensor tree_leaf_off,
+                         at::Tensor leaf_off, at::Tensor leaf_val,
+                         at::Tensor elem_code, at::Tensor elem_z,
+                         int64_t n_trees, int64_t F) {
+    TORCH_CHECK(codes.is_cuda() && codes.dtype() == at::kByte &&
+                codes.dim() == 2 && codes.size(1) == FPAD &&
+                codes.is_contiguous());
+    TORCH_CHECK(F >= 1 && F <= FPAD);
+    TORCH_CHECK(n_trees >= 1 && n_trees <= 65535,
+                "detector_shap: tree count out of range");
+    for (const at::Tensor* p : {&tree_leaf_off, &leaf_off, &elem_code})
+        TORCH_CHECK(p->is_cuda() && p->dtype() == at::kInt &&
+                    p->dim() == 1 && p->is_contiguous());
+    for (const at::Tensor* p : {&leaf_val, &elem_z})
+        TORCH_CHECK(p->is_cuda() && p->dtype() == at::kDouble &&
+                    p->dim() == 1 && p->is_contiguous());
+    const long L = leaf_val.numel(), E = elem_z.numel();
+    TORCH_CHECK(tree_leaf_off.numel() == n_trees + 1 &&
+                leaf_off.numel() == L + 1 && elem_code.numel() == E &&
+                L >= n_trees && L < (1L << 31) && E < (1L << 31),
+                "detector_shap: path table sizes");
+    const long M = codes.size(0);
+    TORCH_CHECK(M < (1L << 31));
+
+    const at::cuda::OptionalCUDAGuard guard(codes.device());
+    auto phi = at::empty({M, FPAD}, codes.options().dtype(at::kDouble));
+    if (M == 0) return phi;
+
+    // offsets start at 0, end at the array they index and never step
+    // back; a tree owns a leaf, a leaf at most F elements, and every
+    // element names a feature below F
+    auto t_step = tree_leaf_off.diff();
+    auto l_step = leaf_off.diff();
+    auto ok = tree_leaf_off[0].eq(0) & tree_leaf_off[n_trees].eq(L) &
+              t_step.ge(1).all() & leaf_off[0].eq(0) &
+              leaf_off[L].eq(E) & l_step.ge(0).all() & l_step.le(F).all();
+    if (E > 0)
+        ok = ok & elem_code.bitwise_and(0xFF).lt(F).all();
+    TORCH_CHECK(ok.item<bool>(), "detector_shap: malformed path table");
+
+    // workspace [T, FPAD, rows] bounded at 256 MiB: rows go in chunks
+    const long ws_cap = 256L << 20;
+    const long per_row = n_trees * FPAD * (long)sizeof(double);
+    long chunk = std::max<long>(EXPLAIN_BLK,
+                                ws_cap / per_row / EXPLAIN_BLK * EXPLAIN_BLK);
+    chunk = std::min(chunk, M);
+    auto partial = at::empty({n_trees * FPAD * chunk},
+                             codes.options().dtype(at::kDouble));
+    hipStream_t s = current_stream();
+    for (long row0 = 0; row0 < M; row0 += chunk) {
+        const int mc = (int)std::min(chunk, M - row0);
+        const int gx = (mc + EXPLAIN_BLK - 1) / EXPLAIN_BLK;
+        detector_shap_tree_kernel<<<dim3(gx, (int)n_trees), EXPLAIN_BLK, 0,
+                                    s>>>(
+            codes.data_ptr<uint8_t>(), tree_leaf_off.data_ptr<int>(),
+            leaf_off.data_ptr<int>(), leaf_val.data_ptr<double>(),
+            E ? elem_code.data_ptr<int>() : nullptr,
+            E ? elem_z.data_ptr<double>() : nullptr, (int)row0, mc,
+            partial.data_ptr<double>());
+        detector_shap_combine_kernel<<<dim3(gx, FPAD), EXPLAIN_BLK, 0, s>>>(
+            partial.data_ptr<double>(), (int)row0, mc, (int)n_trees,
+            phi.data_ptr<double>());
+    }
+    return phi;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("treeshap", &treeshap, py::call_guard<py::gil_scoped_release>(),
           "Path-dependent TreeSHAP (class-0), summed over trees");
@@ -809,4 +883,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("forest_proba", &forest_proba,
           py::call_guard<py::gil_scoped_release>(),
           "Per-row class-probability sums over a packed forest");
+    m.def("detector_shap", &detector_shap,
+          py::call_guard<py::gil_scoped_release>(),
+          "Per-row class-1 TreeSHAP over a detector's merged leaf paths");
 }

@@ -28,6 +28,7 @@ setup(
                      "flake16_framework_amd/ops/hip/scaler_pca.hip",
                      "flake16_framework_amd/ops/hip/treeshap.hip",
                      "flake16_framework_amd/ops/hip/detect.hip",
+                     "flake16_framework_amd/ops/hip/explain.hip",
                      "flake16_framework_amd/ops/hip/philox.h"],
             extra_compile_args={
                 "cxx": ["-O3"],
