@@ -173,8 +173,12 @@ __global__ void knn_segmented_kernel(const float* __restrict__ X,
 // so the output bits match the numpy reference exactly.  A query whose
 // phase-1 list provably may have dropped a contender (discard_min within
 // the error bound of the pooled kth distance) falls back to the scalar
-// exact scan (knn_fallback_kernel); with continuous features this is
-// rare-to-never.
+// exact scan (knn_fallback_kernel).  On continuous or scaled features
+// this is rare (0 queries on the bench workload).  On raw integer features
+// it is routine and is what makes the output correct: more equidistant
+// candidates than a lane's list holds (duplicate rows), or distances far
+// below the fp32 resolution of the squared norms (large common offset),
+// send every query of the segment there.
 //
 // Error bound: |d32 - d| <= ~40 eps32 M (M = max squared row norm of the
 // segment, ~20 roundings of magnitude <= 4M); the pool slack uses
