@@ -34,6 +34,7 @@
 #include <cstdint>
 
 #include "philox.h"
+#include "wave_ops.h"
 
 #define HBLK 256
 #define FPAD 16          // codes row stride (bytes); F <= 16
@@ -1161,6 +1162,36 @@ struct MidFrame {
 #define MID_STACK 96
 #define WAVE_CANDS 4   // wave-parallel path: max_features <= 4 (RF / ET)
 
+// m_idx / m_idx2 entries: local sample index (11 bits for MID_N = 2048)
+// with the sample's label in bit 15, set once at staging, so no pass reads
+// a separate label array.  Partitions move the entry whole; the write-back
+// masks the bit.
+#define MID_LAB_BIT 15
+#define MID_IDX_MASK 0x7FFF
+
+// A <= SMALL_N child of a mid item goes to the global small queue with its
+// final global range and the mid item's buffer tag (the write-back lands
+// in the mid root's buffer).  Called by one thread.
+__device__ __forceinline__ void mid_farm_small(
+    const ForestDev& a, const WorkItem& it, int s, int e, int depth,
+    int node) {
+    const int i = atomicAdd(a.small_count, 1);
+    if (i < a.small_cap)
+        a.small[i] = {it.job, node, it.start + s, it.start + e, depth,
+                      it.hist_slot};
+    else
+        atomicExch(a.err_flag, 1);
+}
+
+// Code of feature f from a 16-byte row.  Selects instead of indexing: a
+// dynamically indexed private array is promoted to LDS (or scratch) by
+// the compiler, which puts a store + load round trip on every sample.
+__device__ __forceinline__ uint32_t code_byte(const uint4& cw, int f) {
+    const int k = f >> 2;
+    const uint32_t w = k == 0 ? cw.x : k == 1 ? cw.y : k == 2 ? cw.z : cw.w;
+    return (w >> ((f & 3) * 8)) & 0xFFu;
+}
+
 // One 64-lane wave splits one node [ls, le) of the staged window and
 // routes its children (shared LDS stack for > SMALL_N, global small queue
 // otherwise).  Control flow is wave-uniform throughout; split semantics,
@@ -1171,20 +1202,16 @@ struct MidFrame {
 template <bool STAGED>
 __device__ __forceinline__ void mid_wave_node(
     const ForestDev& a, const WorkItem& it, int ls, int le, int depth,
-    int node, const uint4* m_codes, const uint8_t* m_lab,
-    const int* m_rows, uint16_t* m_idx,
-    uint16_t* m_idx2, uint32_t* whist, int* wperm, uint32_t* wthr,
-    int* wcand, int* wcbin, MidFrame* stack, int* sh_count) {
-    // STAGED reads the LDS-staged code rows / labels; the unstaged
-    // variant reads them from L1/L2 through the m_rows map (half the
-    // LDS per block -> double the resident blocks).
+    int node, const uint4* m_codes, const int* m_rows, uint16_t* m_idx,
+    uint16_t* m_idx2, uint32_t* whist, MidFrame* stack,
+    int* sh_count) {
+    // STAGED reads the LDS-staged code rows; the unstaged variant reads
+    // them from L1/L2 through the m_rows map (half the LDS per block).
+    // m_idx entries carry the sample's label in bit 15 (MID_LAB_BIT).
     auto code_at = [&](int o) -> uint4 {
         if (STAGED) return m_codes[o];
         return *reinterpret_cast<const uint4*>(
             a.codes + (size_t)m_rows[o] * FPAD);
-    };
-    auto lab_at = [&](int o) -> int {
-        return STAGED ? (int)m_lab[o] : (int)a.labels[m_rows[o]];
     };
     const int lane = threadIdx.x & 63;
     const int n = le - ls;
@@ -1196,36 +1223,34 @@ __device__ __forceinline__ void mid_wave_node(
     const int gs = it.start + ls;   // global job-relative range (RNG id)
     const int ge = it.start + le;
 
-    // Pass 1: per-feature occupied min/max + class-1 count.
-    int lmin[FPAD], lmax[FPAD];
+    // Pass 1: per-feature occupied min/max + class-1 count.  Each code
+    // word is unpacked into two u16 pairs, so one packed min and one
+    // packed max cover two features: pmin[2k] holds features 4k (low
+    // half) and 4k+2 (high half), pmin[2k+1] features 4k+1 and 4k+3.
+    // Only the words that hold a feature < F are touched.
+    const int nw = (F + 3) >> 2;
+    uint32_t pmin[FPAD / 2], pmax[FPAD / 2];
     #pragma unroll
-    for (int f = 0; f < FPAD; ++f) { lmin[f] = 256; lmax[f] = -1; }
+    for (int k = 0; k < FPAD / 2; ++k) { pmin[k] = 0x01000100u; pmax[k] = 0u; }
     int lc1 = 0;
     for (int i = ls + lane; i < le; i += 64) {
-        const int o = m_idx[i];
-        const uint4 cw = code_at(o);
+        const int ent = m_idx[i];
+        const uint4 cw = code_at(ent & MID_IDX_MASK);
         const uint32_t w[4] = {cw.x, cw.y, cw.z, cw.w};
-        lc1 += lab_at(o);
+        lc1 += ent >> MID_LAB_BIT;
         #pragma unroll
-        for (int f = 0; f < FPAD; ++f) {
-            const int b = (int)((w[f >> 2] >> ((f & 3) * 8)) & 0xFFu);
-            lmin[f] = min(lmin[f], b);
-            lmax[f] = max(lmax[f], b);
+        for (int k = 0; k < FPAD / 4; ++k) {
+            if (k >= nw) break;
+            const uint32_t ev = w[k] & 0x00FF00FFu;
+            const uint32_t od = (w[k] >> 8) & 0x00FF00FFu;
+            pmin[2 * k] = pkmin_u16x2(pmin[2 * k], ev);
+            pmax[2 * k] = pkmax_u16x2(pmax[2 * k], ev);
+            pmin[2 * k + 1] = pkmin_u16x2(pmin[2 * k + 1], od);
+            pmax[2 * k + 1] = pkmax_u16x2(pmax[2 * k + 1], od);
         }
     }
-    for (int d = 32; d > 0; d >>= 1) lc1 += __shfl_down(lc1, d);
-    const int c1 = __shfl(lc1, 0);
+    const int c1 = wave_sum_i32(lc1);
     const int c0 = n - c1;
-    #pragma unroll
-    for (int f = 0; f < FPAD; ++f) {
-        int mn = lmin[f], mx = lmax[f];
-        for (int d = 32; d > 0; d >>= 1) {
-            mn = min(mn, __shfl_xor(mn, d));
-            mx = max(mx, __shfl_xor(mx, d));
-        }
-        lmin[f] = mn;   // wave-uniform from here on
-        lmax[f] = mx;
-    }
 
     if (lane == 0) {
         a.ncnt0[nbase + node] = (float)c0;
@@ -1233,76 +1258,85 @@ __device__ __forceinline__ void mid_wave_node(
     }
     if (n < 2 || c0 == 0 || c1 == 0) return;   // leaf
 
-    // Feature permutation + candidate walk (draws parallel across lanes,
-    // walk on lane 0 through this wave's LDS scratch).
-    {
-        const uint32_t uf = philox_draw(
-            TAG_FEATSEL | ((uint32_t)(depth & 0xFF) << 8),
+    // Cross-lane reduction; the results are wave-uniform.  Lane f < 16
+    // then keeps feature f's range as (min | max << 16) in rng_mine, so
+    // the candidate walk fetches a range with one v_readlane and never
+    // indexes a register array dynamically.
+    uint32_t rng_mine = 0;
+    #pragma unroll
+    for (int k = 0; k < FPAD / 4; ++k) {
+        if (k >= nw) break;
+        #pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const uint32_t umin = wave_pkmin_u16x2(pmin[2 * k + h]);
+            const uint32_t umax = wave_pkmax_u16x2(pmax[2 * k + h]);
+            // low halves: feature 4k + h; high halves: feature 4k + h + 2
+            if (lane == 4 * k + h)
+                rng_mine = (umin & 0xFFFFu) | (umax << 16);
+            if (lane == 4 * k + h + 2)
+                rng_mine = (umin >> 16) | (umax & 0xFFFF0000u);
+        }
+    }
+
+    // Feature permutation + candidate walk, wave-uniform in registers:
+    // candidates, their ranges and (ET) drawn bins are packed 4 / 8 bits
+    // per candidate (WAVE_CANDS = 4 candidates, values <= 255).
+    const uint64_t perm = feature_perm(
+        philox_draw(TAG_FEATSEL | ((uint32_t)(depth & 0xFF) << 8),
+                    (uint32_t)gs, (uint32_t)ge,
+                    (uint32_t)(lane < FPAD ? lane : 0), a.seed, key),
+        F);
+    uint32_t thr_mine = 0;
+    if (splitter_random)
+        thr_mine = philox_draw(
+            TAG_THRESH | ((uint32_t)(depth & 0xFF) << 8),
             (uint32_t)gs, (uint32_t)ge,
             (uint32_t)(lane < FPAD ? lane : 0), a.seed, key);
-        if (splitter_random && lane < FPAD)
-            wthr[lane] = philox_draw(
-                TAG_THRESH | ((uint32_t)(depth & 0xFF) << 8),
-                (uint32_t)gs, (uint32_t)ge, (uint32_t)lane, a.seed, key);
-        if (lane == 0)
-            for (int f = 0; f < F; ++f) wperm[f] = f;
-        for (int i = 0; i < F - 1; ++i) {
-            const uint32_t u = __shfl(uf, i);
-            if (lane == 0) {
-                int j = i + (int)philox_bounded(u, (uint32_t)(F - i));
-                int t = wperm[i]; wperm[i] = wperm[j]; wperm[j] = t;
-            }
-        }
-    }
     int ncand = 0;
-    if (lane == 0) {
-        for (int i = 0; i < F && ncand < max_features; ++i) {
-            const int f = wperm[i];
-            if (lmin[f] == lmax[f]) continue;
-            wcand[ncand] = f;
-            if (splitter_random)
-                wcbin[ncand] = lmin[f] + (int)philox_bounded(
-                    wthr[f], (uint32_t)(lmax[f] - lmin[f]));
-            ++ncand;
-        }
+    uint32_t cand_pk = 0, cbin_pk = 0, cmin_pk = 0, cmax_pk = 0;
+    for (int i = 0; i < F && ncand < max_features; ++i) {
+        const int f = perm_at(perm, i);
+        const uint32_t r = wave_bcast(rng_mine, f);
+        const int mn = (int)(r & 0xFFFFu), mx = (int)(r >> 16);
+        if (mn == mx) continue;
+        cand_pk |= (uint32_t)f << (4 * ncand);
+        cmin_pk |= (uint32_t)mn << (8 * ncand);
+        cmax_pk |= (uint32_t)mx << (8 * ncand);
+        if (splitter_random)
+            cbin_pk |= (uint32_t)(mn + (int)philox_bounded(
+                wave_bcast(thr_mine, f), (uint32_t)(mx - mn)))
+                       << (8 * ncand);
+        ++ncand;
     }
-    ncand = __shfl(ncand, 0);
     if (ncand == 0) return;   // all candidates constant: leaf
 
     double best_s = -1.0e300;
     int bf = -1, bb = -1, bnl = 0;
 
     if (splitter_random) {
-        // ET: counts at each candidate's drawn bin — histogram-free.
-        int cnt[WAVE_CANDS], cnt1[WAVE_CANDS];
+        // ET: counts at each candidate's drawn bin — histogram-free.  The
+        // left count (low half) and its class-1 part (high half) share one
+        // accumulator: n <= MID_N = 2048 fits 16 bits.
+        int cnt[WAVE_CANDS];
         #pragma unroll
-        for (int ci = 0; ci < WAVE_CANDS; ++ci) { cnt[ci] = 0; cnt1[ci] = 0; }
+        for (int ci = 0; ci < WAVE_CANDS; ++ci) cnt[ci] = 0;
         for (int i = ls + lane; i < le; i += 64) {
-            const int o = m_idx[i];
-            const uint4 cw = code_at(o);
-            const uint32_t w[4] = {cw.x, cw.y, cw.z, cw.w};
-            const int lab = lab_at(o);
+            const int ent = m_idx[i];
+            const uint4 cw = code_at(ent & MID_IDX_MASK);
+            const int inc = 1 | ((ent >> MID_LAB_BIT) << 16);
             #pragma unroll
             for (int ci = 0; ci < WAVE_CANDS; ++ci) {
                 if (ci >= ncand) break;
-                const int f = wcand[ci];
-                const int b = (int)((w[f >> 2] >> ((f & 3) * 8)) & 0xFFu);
-                const int le_ = b <= wcbin[ci];
-                cnt[ci] += le_;
-                cnt1[ci] += le_ & lab;
+                const int f = (int)((cand_pk >> (4 * ci)) & 15u);
+                const int b = (int)code_byte(cw, f);
+                cnt[ci] += b <= (int)((cbin_pk >> (8 * ci)) & 0xFFu) ? inc : 0;
             }
         }
         #pragma unroll
         for (int ci = 0; ci < WAVE_CANDS; ++ci) {
             if (ci >= ncand) break;
-            int c = cnt[ci], cl = cnt1[ci];
-            for (int d = 32; d > 0; d >>= 1) {
-                c += __shfl_down(c, d);
-                cl += __shfl_down(cl, d);
-            }
-            c = __shfl(c, 0);
-            cl = __shfl(cl, 0);
-            const long nL = c, n1L = cl;
+            const int tot = wave_sum_i32(cnt[ci]);
+            const long nL = tot & 0xFFFF, n1L = tot >> 16;
             const long n0L = nL - n1L, nR = n - nL;
             const long n1R = c1 - n1L, n0R = c0 - n0L;
             if (nL == 0 || nR == 0) continue;
@@ -1310,8 +1344,8 @@ __device__ __forceinline__ void mid_wave_node(
                             + (double)(n0R * n0R + n1R * n1R) / (double)nR;
             if (sc > best_s) {
                 best_s = sc;
-                bf = wcand[ci];
-                bb = wcbin[ci];
+                bf = (int)((cand_pk >> (4 * ci)) & 15u);
+                bb = (int)((cbin_pk >> (8 * ci)) & 0xFFu);
                 bnl = (int)nL;
             }
         }
@@ -1319,21 +1353,20 @@ __device__ __forceinline__ void mid_wave_node(
         // RF: candidate-only packed LDS histograms.
         for (int i = lane; i < ncand * 256; i += 64) whist[i] = 0;
         for (int i = ls + lane; i < le; i += 64) {
-            const int o = m_idx[i];
-            const uint4 cw = code_at(o);
-            const uint32_t w[4] = {cw.x, cw.y, cw.z, cw.w};
-            const uint32_t inc = 1u | ((uint32_t)lab_at(o) << 16);
+            const int ent = m_idx[i];
+            const uint4 cw = code_at(ent & MID_IDX_MASK);
+            const uint32_t inc = 1u | ((uint32_t)(ent >> MID_LAB_BIT) << 16);
             #pragma unroll
             for (int ci = 0; ci < WAVE_CANDS; ++ci) {
                 if (ci >= ncand) break;
-                const int f = wcand[ci];
-                const uint32_t b = (w[f >> 2] >> ((f & 3) * 8)) & 0xFFu;
+                const int f = (int)((cand_pk >> (4 * ci)) & 15u);
+                const uint32_t b = code_byte(cw, f);
                 atomicAdd(&whist[ci * 256 + b], inc);
             }
         }
         for (int ci = 0; ci < ncand; ++ci) {
-            const int f = wcand[ci];
-            const int bmin = lmin[f], bmax = lmax[f];
+            const int bmin = (int)((cmin_pk >> (8 * ci)) & 0xFFu);
+            const int bmax = (int)((cmax_pk >> (8 * ci)) & 0xFFu);
             int ln[4], l1[4];
             int tn = 0, t1 = 0;
             #pragma unroll
@@ -1344,13 +1377,9 @@ __device__ __forceinline__ void mid_wave_node(
                 tn += ln[k];
                 t1 += l1[k];
             }
-            int scn = tn, sc1 = t1;
-            for (int d = 1; d < 64; d <<= 1) {
-                const int un = __shfl_up(scn, d);
-                const int u1 = __shfl_up(sc1, d);
-                if (lane >= d) { scn += un; sc1 += u1; }
-            }
-            int cn = scn - tn, c1f = sc1 - t1;
+            // both counts in one scan: n <= MID_N fits 16 bits each
+            const int sc = wave_scan_incl_i32(tn | (t1 << 16));
+            int cn = (sc & 0xFFFF) - tn, c1f = (sc >> 16) - t1;
             double cand_s = -1.0;
             int cand_b = -1, cand_nl = 0;
             #pragma unroll
@@ -1367,22 +1396,11 @@ __device__ __forceinline__ void mid_wave_node(
                     + (double)(n0R * n0R + n1R * n1R) / (double)nR;
                 if (s > cand_s) { cand_s = s; cand_b = b; cand_nl = (int)nL; }
             }
-            for (int d = 32; d > 0; d >>= 1) {
-                const double os = __shfl_down(cand_s, d);
-                const int ob = __shfl_down(cand_b, d);
-                const int onl = __shfl_down(cand_nl, d);
-                if (os > cand_s || (os == cand_s && ob != -1 &&
-                                    (cand_b == -1 || ob < cand_b))) {
-                    cand_s = os; cand_b = ob; cand_nl = onl;
-                }
-            }
-            cand_s = __shfl(cand_s, 0);
-            cand_b = __shfl(cand_b, 0);
-            cand_nl = __shfl(cand_nl, 0);
+            wave_argmax_mid(cand_s, cand_b, cand_nl);
             // sequential select in perm order, strict > (phase-6 contract)
             if (cand_b >= 0 && cand_s > best_s) {
                 best_s = cand_s;
-                bf = wcand[ci];
+                bf = (int)((cand_pk >> (4 * ci)) & 15u);
                 bb = cand_b;
                 bnl = cand_nl;
             }
@@ -1401,10 +1419,11 @@ __device__ __forceinline__ void mid_wave_node(
         a.nsplit[nbase + node] = bb;
         a.nleft[nbase + node] = lid;
     }
-    lid = __shfl(lid, 0);
+    lid = wave_bcast(lid, 0);
 
     // Stable partition of m_idx[ls, le) via this node's private m_idx2
-    // range (sibling ranges are disjoint — no cross-wave aliasing).
+    // range (sibling ranges are disjoint — no cross-wave aliasing).  The
+    // entry moves whole: its label bit travels with the index.
     int lo = 0, ro = 0;
     for (int base = ls; base < le; base += 64) {
         const int i = base + lane;
@@ -1412,10 +1431,8 @@ __device__ __forceinline__ void mid_wave_node(
         int o = 0, flag = 0;
         if (valid) {
             o = m_idx[i];
-            const uint4 cw = code_at(o);
-            const uint32_t wsel = (&cw.x)[bf >> 2];
-            flag = (int)(((wsel >> ((bf & 3) * 8)) & 0xFFu)
-                         <= (uint32_t)bb);
+            const uint4 cw = code_at(o & MID_IDX_MASK);
+            flag = (int)(code_byte(cw, bf) <= (uint32_t)bb);
         }
         const unsigned long long lm = __ballot(valid && flag);
         const unsigned long long below = (1ULL << lane) - 1ULL;
@@ -1437,30 +1454,21 @@ __device__ __forceinline__ void mid_wave_node(
     // global small queue with final global ranges and this mid item's
     // buffer tag (the write-back lands in the mid root's buffer).
     if (lane == 0) {
-        const MidFrame kids[2] = {
-            {(short)ls, (short)(ls + nL), depth + 1, lid},
-            {(short)(ls + nL), (short)le, depth + 1, lid + 1},
-        };
-        for (int x = 0; x < 2; ++x) {
-            const MidFrame& fr = kids[x];
-            const int fn = fr.e - fr.s;
-            if (fn > SMALL_N) {
+        auto route = [&](int s, int e, int child) {
+            if (e - s > SMALL_N) {
                 const int idx = atomicAdd(sh_count, 1);
                 if (idx < MID_STACK) {
-                    stack[idx] = fr;
+                    stack[idx] = {(short)s, (short)e, depth + 1, child};
                 } else {
                     atomicSub(sh_count, 1);
                     atomicExch(a.err_flag, 1);   // unreachable (MID_STACK)
                 }
             } else {
-                const int i2 = atomicAdd(a.small_count, 1);
-                if (i2 < a.small_cap)
-                    a.small[i2] = {it.job, fr.node, it.start + fr.s,
-                                   it.start + fr.e, fr.depth, it.hist_slot};
-                else
-                    atomicExch(a.err_flag, 1);
+                mid_farm_small(a, it, s, e, depth + 1, child);
             }
-        }
+        };
+        route(ls, ls + nL, lid);
+        route(ls + nL, le, lid + 1);
     }
 }
 
@@ -1468,28 +1476,23 @@ template <bool STAGED>
 __launch_bounds__(HBLK)
 __global__ void mid_subtree_kernel(ForestDev a) {
     __shared__ uint4 m_codes[STAGED ? MID_N : 1];   // 32 KiB staged rows
-    __shared__ int m_rows[MID_N];             // 4 KiB original global rows
-    __shared__ uint8_t m_lab[STAGED ? MID_N : 1];   // 2 KiB labels
-    __shared__ uint16_t m_idx[MID_N];         // 2 KiB sample ordering
-    __shared__ uint16_t m_idx2[MID_N];        // 2 KiB partition scratch
+    __shared__ int m_rows[MID_N];             // 8 KiB original global rows
+    // sample ordering / partition scratch, 4 KiB each: local index with
+    // the label in bit 15 (MID_LAB_BIT)
+    __shared__ uint16_t m_idx[MID_N];
+    __shared__ uint16_t m_idx2[MID_N];
     __shared__ uint32_t hist[FPAD * 256];     // 16 KiB packed histogram
     __shared__ int sh_scan[HBLK];
     __shared__ int sh_bmin[FPAD], sh_bmax[FPAD];
     __shared__ int sh_cand[FPAD], sh_ncand;
-    __shared__ uint32_t sh_draws[FPAD];
     __shared__ double sh_score[FPAD];
     __shared__ int sh_bin[FPAD], sh_nL[FPAD];
     __shared__ int sh_bestf, sh_bestbin, sh_bestnL, sh_lid;
     __shared__ MidFrame stack[MID_STACK];
-    __shared__ int sh_sp;
     __shared__ int sh_lo, sh_ro;
-    // wave-parallel mode scratch (one slice per wave)
+    // this round's frames (one per wave in wave-parallel mode)
     __shared__ MidFrame wframes[HBLK / 64];
-    __shared__ int wperm_ws[HBLK / 64][FPAD];
-    __shared__ uint32_t wthr_ws[HBLK / 64][FPAD];
-    __shared__ int wcand_ws[HBLK / 64][WAVE_CANDS];
-    __shared__ int wcbin_ws[HBLK / 64][WAVE_CANDS];
-    __shared__ int sh_count, sh_take;
+    __shared__ int sh_count, sh_take, sh_nblock;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -1511,12 +1514,10 @@ __global__ void mid_subtree_kernel(ForestDev a) {
         for (int i = tid; i < n0; i += HBLK) {
             const int row = sidx_it[sbase + it.start + i];
             m_rows[i] = row;
-            if (STAGED) {
+            if (STAGED)
                 m_codes[i] = *reinterpret_cast<const uint4*>(
                     a.codes + (size_t)row * FPAD);
-                m_lab[i] = a.labels[row];
-            }
-            m_idx[i] = (uint16_t)i;
+            m_idx[i] = (uint16_t)(i | ((a.labels[row] != 0) << MID_LAB_BIT));
         }
 
         auto code_at = [&](int o) -> uint4 {
@@ -1524,16 +1525,12 @@ __global__ void mid_subtree_kernel(ForestDev a) {
             return *reinterpret_cast<const uint4*>(
                 a.codes + (size_t)m_rows[o] * FPAD);
         };
-        auto lab_at = [&](int o) -> int {
-            return STAGED ? (int)m_lab[o] : (int)a.labels[m_rows[o]];
-        };
 
         // Per-node block-wide builder (histogram, split, partition over
         // the staged window) shared by the DFS path and the wave mode's
-        // single-frontier rounds.  dfs_mode selects the child routing:
-        // the DFS stack (smaller child on top) or the wave stack.
-        auto block_node = [&](int ls, int le, int depth, int node,
-                              bool dfs_mode) {
+        // small-frontier rounds; > SMALL_N children go on the stack with
+        // the smaller one on top.
+        auto block_node = [&](int ls, int le, int depth, int node) {
             const int n = le - ls;
             const int max_features = a.j_mf[it.job];
             const int splitter_random = a.j_rand[it.job];
@@ -1546,12 +1543,15 @@ __global__ void mid_subtree_kernel(ForestDev a) {
                 reinterpret_cast<uint4*>(hist)[i] = uint4{0, 0, 0, 0};
             __syncthreads();
             for (int i = ls + tid; i < le; i += HBLK) {
-                const int o = m_idx[i];
-                const uint4 cw = code_at(o);
+                const int ent = m_idx[i];
+                const uint4 cw = code_at(ent & MID_IDX_MASK);
                 const uint32_t w[4] = {cw.x, cw.y, cw.z, cw.w};
-                const uint32_t inc = 1u | ((uint32_t)lab_at(o) << 16);
-                for (int f = 0; f < F; ++f) {
-                    uint32_t b = (w[f >> 2] >> ((f & 3) * 8)) & 0xFFu;
+                const uint32_t inc =
+                    1u | ((uint32_t)(ent >> MID_LAB_BIT) << 16);
+                #pragma unroll
+                for (int f = 0; f < FPAD; ++f) {   // static word indices
+                    if (f >= F) break;
+                    const uint32_t b = (w[f >> 2] >> ((f & 3) * 8)) & 0xFFu;
                     atomicAdd(&hist[f * 256 + b], inc);
                 }
             }
@@ -1559,8 +1559,7 @@ __global__ void mid_subtree_kernel(ForestDev a) {
 
             // class counts (wave reduce over feature-0 histogram)
             {
-                int v = (int)(hist[tid] >> 16);
-                for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
+                const int v = wave_sum_i32((int)(hist[tid] >> 16));
                 if (lane == 0) sh_scan[wave] = v;
             }
             __syncthreads();
@@ -1601,27 +1600,22 @@ __global__ void mid_subtree_kernel(ForestDev a) {
             }
             __syncthreads();
 
-            // permutation + candidate walk (parallel draws)
-            if (tid < FPAD)
-                sh_draws[tid] = philox_draw(
-                    TAG_FEATSEL | ((uint32_t)(depth & 0xFF) << 8),
-                    (uint32_t)gs, (uint32_t)ge, (uint32_t)tid,
-                    a.seed, key);
-            __syncthreads();
-            if (tid == 0) {
-                int perm[FPAD];
-                for (int f = 0; f < F; ++f) perm[f] = f;
-                for (int i = 0; i < F - 1; ++i) {
-                    int j = i + (int)philox_bounded(sh_draws[i],
-                                                    (uint32_t)(F - i));
-                    int t = perm[i]; perm[i] = perm[j]; perm[j] = t;
+            // permutation (wave 0, in a register) + candidate walk
+            if (wave == 0) {
+                const uint64_t perm = feature_perm(
+                    philox_draw(TAG_FEATSEL | ((uint32_t)(depth & 0xFF) << 8),
+                                (uint32_t)gs, (uint32_t)ge,
+                                (uint32_t)(lane < FPAD ? lane : 0),
+                                a.seed, key),
+                    F);
+                if (lane == 0) {
+                    int nc = 0;
+                    for (int i = 0; i < F && nc < max_features; ++i) {
+                        const int f = perm_at(perm, i);
+                        if (sh_bmin[f] != sh_bmax[f]) sh_cand[nc++] = f;
+                    }
+                    sh_ncand = nc;
                 }
-                int nc = 0;
-                for (int i = 0; i < F && nc < max_features; ++i) {
-                    int f = perm[i];
-                    if (sh_bmin[f] != sh_bmax[f]) sh_cand[nc++] = f;
-                }
-                sh_ncand = nc;
             }
             __syncthreads();
 
@@ -1645,13 +1639,10 @@ __global__ void mid_subtree_kernel(ForestDev a) {
                     tn += ln[k];
                     t1 += l1[k];
                 }
-                int scn = tn, sc1 = t1;
-                for (int d = 1; d < 64; d <<= 1) {
-                    int un = __shfl_up(scn, d);
-                    int u1 = __shfl_up(sc1, d);
-                    if (lane >= d) { scn += un; sc1 += u1; }
-                }
-                const int excl_n = scn - tn, excl_1 = sc1 - t1;
+                // both counts in one scan: n <= MID_N fits 16 bits each
+                const int scp = wave_scan_incl_i32(tn | (t1 << 16));
+                const int excl_n = (scp & 0xFFFF) - tn;
+                const int excl_1 = (scp >> 16) - t1;
 
                 double best_s = -1.0;
                 int best_b = -1, best_nl = 0;
@@ -1666,7 +1657,9 @@ __global__ void mid_subtree_kernel(ForestDev a) {
                         u, (uint32_t)(bmax - bmin));
                     if (b >= lane * 4 && b < lane * 4 + 4) {
                         int cn = excl_n, c1f = excl_1;
-                        for (int k = 0; k <= b - lane * 4; ++k) {
+                        #pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            if (k > b - lane * 4) break;
                             cn += ln[k];
                             c1f += l1[k];
                         }
@@ -1699,15 +1692,7 @@ __global__ void mid_subtree_kernel(ForestDev a) {
                         }
                     }
                 }
-                for (int d = 32; d > 0; d >>= 1) {
-                    double os = __shfl_down(best_s, d);
-                    int ob = __shfl_down(best_b, d);
-                    int onl = __shfl_down(best_nl, d);
-                    if (os > best_s || (os == best_s && ob != -1 &&
-                                        (best_b == -1 || ob < best_b))) {
-                        best_s = os; best_b = ob; best_nl = onl;
-                    }
-                }
+                wave_argmax_mid(best_s, best_b, best_nl);
                 if (lane == 0) {
                     sh_score[ci] = best_s;
                     sh_bin[ci] = best_b;
@@ -1758,11 +1743,9 @@ __global__ void mid_subtree_kernel(ForestDev a) {
                 const bool valid = i < le;
                 int o = 0, flag = 0;
                 if (valid) {
-                    o = m_idx[i];
-                    const uint4 cw = code_at(o);
-                    const uint32_t wsel = (&cw.x)[bf >> 2];
-                    flag = (int)(((wsel >> ((bf & 3) * 8)) & 0xFFu)
-                                 <= (uint32_t)bb);
+                    o = m_idx[i];   // whole entry: the label bit moves too
+                    const uint4 cw = code_at(o & MID_IDX_MASK);
+                    flag = (int)(code_byte(cw, bf) <= (uint32_t)bb);
                 }
                 const unsigned long long lm = __ballot(valid && flag);
                 const unsigned long long below = (1ULL << lane) - 1ULL;
@@ -1793,111 +1776,80 @@ __global__ void mid_subtree_kernel(ForestDev a) {
             __syncthreads();
 
             if (tid == 0) {
-                const int nR = n - nL;
-                const MidFrame left = {(short)ls, (short)(ls + nL),
-                                       depth + 1, sh_lid};
-                const MidFrame right = {(short)(ls + nL), (short)le,
-                                        depth + 1, sh_lid + 1};
-                const bool left_small = nL <= nR;
-                const MidFrame* ordered[2] = {
-                    left_small ? &right : &left,   // larger pushed first
-                    left_small ? &left : &right,
-                };
-                for (int x = 0; x < 2; ++x) {
-                    const MidFrame& fr = *ordered[x];
-                    const int fn = fr.e - fr.s;
-                    if (fn <= SMALL_N) {
-                        const int i = atomicAdd(a.small_count, 1);
-                        if (i < a.small_cap)
-                            a.small[i] = {it.job, fr.node,
-                                          it.start + fr.s, it.start + fr.e,
-                                          fr.depth, it.hist_slot};
-                        else
-                            atomicExch(a.err_flag, 1);
-                    } else if (dfs_mode) {
-                        stack[++sh_sp] = fr;
-                    } else if (sh_count < MID_STACK) {
-                        stack[sh_count++] = fr;
-                    } else {
+                auto route = [&](int s, int e, int child) {
+                    if (e - s <= SMALL_N)
+                        mid_farm_small(a, it, s, e, depth + 1, child);
+                    else if (sh_count < MID_STACK)
+                        stack[sh_count++] =
+                            {(short)s, (short)e, depth + 1, child};
+                    else
                         atomicExch(a.err_flag, 1);   // unreachable
-                    }
+                };
+                const int lid = sh_lid, mid = ls + nL;
+                if (nL <= n - nL) {   // larger pushed first
+                    route(mid, le, lid + 1);
+                    route(ls, mid, lid);
+                } else {
+                    route(ls, mid, lid);
+                    route(mid, le, lid + 1);
                 }
             }
             __syncthreads();
         };
 
-        if (a.wave_mid && a.j_mf[it.job] <= WAVE_CANDS) {
-            // Wave-parallel rounds: up to HBLK/64 nodes in flight, each
-            // built by one wave (no block barriers inside a node); a
-            // single-node frontier — the top of every staged subtree —
-            // is built block-wide instead, so no wave idles there.  The
-            // block-wide 16 KiB `hist` array is re-sliced as one
-            // WAVE_CANDS*256-word histogram region per wave.
-            if (tid == 0) {
-                sh_count = 1;
-                stack[0] = {0, (short)n0, it.depth, it.node};
-            }
-            while (true) {
-                __syncthreads();
-                if (tid == 0) {
-                    const int take = min(HBLK / 64, sh_count);
-                    for (int w = 0; w < take; ++w)
-                        wframes[w] = stack[sh_count - 1 - w];
-                    sh_count -= take;
-                    sh_take = take;
-                }
-                __syncthreads();
-                if (sh_take == 0) break;
-                if (sh_take == 1) {
-                    const MidFrame fr = wframes[0];
-                    block_node(fr.s, fr.e, fr.depth, fr.node, false);
-                } else if (sh_take == 2 &&
-                           (wframes[0].e - wframes[0].s)
-                               + (wframes[1].e - wframes[1].s) > 1024) {
-                    // two big frontier nodes: sequential block-wide
-                    // processing beats two waves with two idle
-                    for (int x = 0; x < 2; ++x) {
-                        const MidFrame fr = wframes[x];
-                        block_node(fr.s, fr.e, fr.depth, fr.node, false);
-                    }
-                } else if (wave < sh_take) {
-                    const MidFrame fr = wframes[wave];
-                    mid_wave_node<STAGED>(
-                        a, it, fr.s, fr.e, fr.depth, fr.node,
-                        m_codes, m_lab, m_rows, m_idx, m_idx2,
-                        hist + wave * (WAVE_CANDS * 256),
-                        wperm_ws[wave], wthr_ws[wave],
-                        wcand_ws[wave], wcbin_ws[wave],
-                        stack, &sh_count);
-                }
-            }
-            __syncthreads();
-            for (int i = tid; i < n0; i += HBLK)
-                sidx_it[sbase + it.start + i] = m_rows[m_idx[i]];
-            __syncthreads();
-            continue;
-        }
-
+        // Rounds over the stack of > SMALL_N frames.  Wave-parallel mode
+        // (max_features <= WAVE_CANDS) takes up to HBLK/64 frames per
+        // round, each built by one wave with no block barrier inside a
+        // node; a single-frame round — the top of every staged subtree —
+        // and a round of two big frames are built block-wide instead, so
+        // no wave idles there.  Block-serial mode (DT) takes one frame per
+        // round: a DFS with the smaller child on top.  The block-wide
+        // 16 KiB `hist` array is re-sliced as one WAVE_CANDS*256-word
+        // histogram region per wave.
+        const int per_round =
+            a.wave_mid && a.j_mf[it.job] <= WAVE_CANDS ? HBLK / 64 : 1;
         if (tid == 0) {
-            sh_sp = 0;
+            sh_count = 1;
             stack[0] = {0, (short)n0, it.depth, it.node};
         }
-        __syncthreads();
-
         while (true) {
-            const int sp = sh_sp;
-            if (sp < 0) break;
-            const MidFrame fr = stack[sp];
             __syncthreads();
-            if (tid == 0) --sh_sp;
-            block_node(fr.s, fr.e, fr.depth, fr.node, true);
+            if (tid == 0) {
+                const int take = min(per_round, sh_count);
+                for (int w = 0; w < take; ++w)
+                    wframes[w] = stack[sh_count - 1 - w];
+                sh_count -= take;
+                sh_take = take;
+                // two big frontier nodes: sequential block-wide processing
+                // beats two waves with two idle
+                sh_nblock =
+                    take == 1 ? 1
+                    : take == 2 && (wframes[0].e - wframes[0].s)
+                                   + (wframes[1].e - wframes[1].s) > 1024
+                        ? 2 : 0;
+            }
+            __syncthreads();
+            const int take = sh_take, nblock = sh_nblock;
+            if (take == 0) break;
+            for (int x = 0; x < nblock; ++x) {
+                const MidFrame fr = wframes[x];
+                block_node(fr.s, fr.e, fr.depth, fr.node);
+            }
+            if (nblock == 0 && wave < take) {
+                const MidFrame fr = wframes[wave];
+                mid_wave_node<STAGED>(
+                    a, it, fr.s, fr.e, fr.depth, fr.node,
+                    m_codes, m_rows, m_idx, m_idx2,
+                    hist + wave * (WAVE_CANDS * 256), stack, &sh_count);
+            }
         }
 
         // write the final arrangement back so the small kernel (launched
         // after this one) reads each farmed subtree's samples
         __syncthreads();
         for (int i = tid; i < n0; i += HBLK)
-            sidx_it[sbase + it.start + i] = m_rows[m_idx[i]];
+            sidx_it[sbase + it.start + i] =
+                m_rows[m_idx[i] & MID_IDX_MASK];
         __syncthreads();
     }
 }
@@ -1909,7 +1861,9 @@ __global__ void mid_subtree_kernel(ForestDev a) {
 // sample's 16 packed codes + label in registers; node membership is a
 // 64-bit lane mask; class/prefix counts come from __ballot+popcount; the
 // DFS stack lives in LDS.  No histograms, no sample-index traffic, no
-// further level round-trips.  All randomness stays keyed on the node's
+// further level round-trips.  The feature permutation, the min/max and
+// argmax reductions and all broadcasts stay in registers (wave_ops.h).
+// All randomness stays keyed on the node's
 // (start, end) range (child ranges follow the stable-partition arithmetic
 // [s, s+nL) / [s+nL, e)), and split scores use the identical fp64
 // expression — trees are bit-identical to the histogram path / numpy
@@ -1925,7 +1879,6 @@ struct SmallFrame {
 __launch_bounds__(HBLK)
 __global__ void small_subtree_kernel(ForestDev a) {
     __shared__ SmallFrame stack_ws[HBLK / 64][SMALL_STACK];
-    __shared__ int perm_ws[HBLK / 64][FPAD];
 
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -1933,7 +1886,6 @@ __global__ void small_subtree_kernel(ForestDev a) {
     const int wave_id = blockIdx.x * (HBLK / 64) + wave;
     const int n_items = min(*a.small_count, a.small_cap);
     SmallFrame* stack = stack_ws[wave];
-    int* perm = perm_ws[wave];
 
     for (int wi = wave_id; wi < n_items; wi += waves_total) {
         const WorkItem it = a.small[wi];
@@ -1982,26 +1934,13 @@ __global__ void small_subtree_kernel(ForestDev a) {
             if (n < 2 || c0 == 0 || c1 == 0) continue;
 
             // feature permutation: each of the first F-1 lanes computes
-            // its Philox draw in parallel; lane 0 runs the swap loop with
-            // the draws broadcast by shuffle
-            {
-                uint32_t tag = TAG_FEATSEL |
-                               ((uint32_t)(depth & 0xFF) << 8);
-                const uint32_t u_mine = philox_draw(
-                    tag, (uint32_t)s, (uint32_t)e,
-                    (uint32_t)(lane < FPAD ? lane : 0), a.seed, key);
-                if (lane == 0)
-                    for (int f = 0; f < F; ++f) perm[f] = f;
-                for (int i = 0; i < F - 1; ++i) {
-                    const uint32_t u = __shfl(u_mine, i);
-                    if (lane == 0) {
-                        int j = i + (int)philox_bounded(
-                            u, (uint32_t)(F - i));
-                        int t = perm[i]; perm[i] = perm[j]; perm[j] = t;
-                    }
-                }
-            }
-            // lane 0's LDS writes are visible to the wave in program order
+            // its Philox draw and swap target in parallel; the swaps run
+            // wave-uniformly in a 64-bit register (wave_ops.h)
+            const uint64_t perm = feature_perm(
+                philox_draw(TAG_FEATSEL | ((uint32_t)(depth & 0xFF) << 8),
+                            (uint32_t)s, (uint32_t)e,
+                            (uint32_t)(lane < FPAD ? lane : 0), a.seed, key),
+                F);
 
             uint32_t u_thresh = 0;
             if (splitter_random) {
@@ -2017,24 +1956,24 @@ __global__ void small_subtree_kernel(ForestDev a) {
             int n_eval = 0;
 
             for (int pi = 0; pi < F && n_eval < max_features; ++pi) {
-                const int f = perm[pi];
+                const int f = perm_at(perm, pi);
                 const int my_code = (int)((w[f >> 2] >> ((f & 3) * 8))
                                           & 0xFFu);
                 const bool in = (mask >> lane) & 1ULL;
-                // occupied-bin range via wave min/max (inactive lanes
-                // neutralized)
-                int cmin = in ? my_code : 256;
-                int cmax = in ? my_code : -1;
-                for (int d = 32; d > 0; d >>= 1) {
-                    cmin = min(cmin, __shfl_xor(cmin, d));
-                    cmax = max(cmax, __shfl_xor(cmax, d));
-                }
+                // occupied-bin range in ONE packed reduction: low half
+                // min(code), high half min(255 - code) = 255 - max(code);
+                // inactive lanes carry the neutral 256 in both halves
+                const uint32_t rng = wave_pkmin_u16x2(
+                    in ? (uint32_t)my_code | ((uint32_t)(255 - my_code) << 16)
+                       : 0x01000100u);
+                const int cmin = (int)(rng & 0xFFFFu);
+                const int cmax = 255 - (int)(rng >> 16);
                 if (cmin == cmax) continue;   // constant: not counted
                 ++n_eval;
 
                 if (splitter_random) {
                     const int b = cmin + (int)philox_bounded(
-                        __shfl(u_thresh, f), (uint32_t)(cmax - cmin));
+                        wave_bcast(u_thresh, f), (uint32_t)(cmax - cmin));
                     const unsigned long long lm =
                         mask & __ballot(in && my_code <= b);
                     const long nL = __popcll(lm);
@@ -2086,17 +2025,7 @@ __global__ void small_subtree_kernel(ForestDev a) {
                         sb = my_code;
                         snl = (int)nL;
                     }
-                    for (int d = 32; d > 0; d >>= 1) {
-                        const double os = __shfl_down(sc, d);
-                        const int ob = __shfl_down(sb, d);
-                        const int onl = __shfl_down(snl, d);
-                        if (os > sc || (os == sc && ob < sb)) {
-                            sc = os; sb = ob; snl = onl;
-                        }
-                    }
-                    sc = __shfl(sc, 0);
-                    sb = __shfl(sb, 0);
-                    snl = __shfl(snl, 0);
+                    wave_argmax_small(sc, sb, snl);
                     if (sc > best_s) {
                         best_s = sc; best_f = f; best_b = sb;
                         best_nl = snl;
@@ -2115,7 +2044,7 @@ __global__ void small_subtree_kernel(ForestDev a) {
                 a.nsplit[nbase + node] = best_b;
                 a.nleft[nbase + node] = lid;
             }
-            lid = __shfl(lid, 0);
+            lid = wave_bcast(lid, 0);
 
             const int bc = (int)((w[best_f >> 2] >> ((best_f & 3) * 8))
                                  & 0xFFu);
