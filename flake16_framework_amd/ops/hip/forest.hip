@@ -26,6 +26,11 @@
 // are bit-identical to the numpy reference in models/forest_ref.py no
 // matter how the device schedules the work.
 //
+// All tiers build a node from the same steps — node draws, fp64 split
+// score, best bin of a histogram row, select in permutation order, commit,
+// stable partition — and each step is written once, in the "Shared node
+// steps" section above the kernels.  A change to a step belongs there.
+//
 // Reference semantics being implemented: sklearn 1.0.2 defaults for
 // DecisionTree/RandomForest/ExtraTrees (see models/forest_ref.py docstring;
 // reference experiment.py:96-98, 469, 473).
@@ -145,6 +150,274 @@ __device__ __forceinline__ void route_child(const ForestDev& a,
     }
 }
 
+// ===========================================================================
+// Shared node steps.
+//
+// The single copy of each step every tier runs to build a node.  Bit-parity
+// with models/forest_ref.py rests on these: the operand order of
+// split_score, the Philox counters, the lowest-bin and first-candidate tie
+// rules, and the stable partition arithmetic.  The wave-level steps assume
+// a fully active 64-lane wave in wave-uniform control flow (wave_ops.h).
+// ===========================================================================
+
+// Code of feature f from a 16-byte row.  Selects instead of indexing: a
+// dynamically indexed private array is promoted to LDS (or scratch) by
+// the compiler, which puts a store + load round trip on every sample.
+__device__ __forceinline__ uint32_t code_byte(const uint4& cw, int f) {
+    const int k = f >> 2;
+    const uint32_t w = k == 0 ? cw.x : k == 1 ? cw.y : k == 2 ? cw.z : cw.w;
+    return (w >> ((f & 3) * 8)) & 0xFFu;
+}
+
+// Packed histogram word -> (total, class-1) counts.
+__device__ __forceinline__ uint2 unpack_counts(uint32_t v) {
+    return uint2{v & 0xFFFFu, v >> 16};
+}
+
+// Sum of v over the block's 256 threads, returned to every thread.
+__device__ __forceinline__ int block_sum_i32(int v, int* sh_wsum) {
+    v = wave_sum_i32(v);
+    if ((threadIdx.x & 63) == 0) sh_wsum[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const int t = sh_wsum[0] + sh_wsum[1] + sh_wsum[2] + sh_wsum[3];
+    __syncthreads();
+    return t;
+}
+
+// Split score of a node (n samples, c0 / c1 per class) whose left child
+// takes nL samples, n1L of them class 1.  fp64 with integer operands; the
+// operand order is forest_ref's (file compiled -ffp-contract=off).  The
+// caller makes sure neither child is empty.
+__device__ __forceinline__ double split_score(long nL, long n1L, int n,
+                                              int c0, int c1) {
+    const long n0L = nL - n1L, nR = n - nL;
+    const long n1R = c1 - n1L, n0R = c0 - n0L;
+    return (double)(n0L * n0L + n1L * n1L) / (double)nL
+         + (double)(n0R * n0R + n1R * n1R) / (double)nR;
+}
+
+// The two per-node Philox draws, keyed on the node's job-relative sample
+// range [s, e) and depth: lane i < FPAD holds draw i (the other lanes
+// repeat draw 0 and are never read).
+__device__ __forceinline__ uint32_t node_draws(
+    uint32_t tag, const ForestDev& a, uint32_t key, int depth, int s, int e) {
+    const int lane = threadIdx.x & 63;
+    return philox_draw(tag | ((uint32_t)(depth & 0xFF) << 8), (uint32_t)s,
+                       (uint32_t)e, (uint32_t)(lane < FPAD ? lane : 0),
+                       a.seed, key);
+}
+// Feature permutation of the node (partial Fisher-Yates, wave_ops.h).
+__device__ __forceinline__ uint64_t featsel_perm(
+    const ForestDev& a, uint32_t key, int depth, int s, int e) {
+    return feature_perm(node_draws(TAG_FEATSEL, a, key, depth, s, e), a.F);
+}
+// Extra-Trees threshold draws: lane f holds feature f's.
+__device__ __forceinline__ uint32_t thresh_draws(
+    const ForestDev& a, uint32_t key, int depth, int s, int e) {
+    return node_draws(TAG_THRESH, a, key, depth, s, e);
+}
+// The drawn bin of feature f (wave-uniform) with occupied range [mn, mx].
+__device__ __forceinline__ int et_bin(uint32_t thr_mine, int f, int mn,
+                                      int mx) {
+    return mn + (int)philox_bounded(wave_bcast(thr_mine, f),
+                                    (uint32_t)(mx - mn));
+}
+
+// Best bin of one 256-bin histogram row, by one wave.  counts(b) returns
+// bin b's (total, class-1) counts; lane l takes bins 4l..4l+3.  Returns,
+// wave-uniform, the best (score, bin, left count) over the occupied bins
+// in [bmin, bmax), the lowest bin winning ties, or bin = -1 if there is
+// none.  Split scores only change at occupied bins, and the first bin of
+// an equal-score run is occupied, so skipping empty bins preserves the
+// argmax-first result.  PACKED_SCAN carries both prefix counts in one
+// scan; it needs n < 2^15 (callers: n <= MID_N).
+template <bool PACKED_SCAN, class CountsFn>
+__device__ __forceinline__ void wave_best_bin(
+    CountsFn counts, int bmin, int bmax, int n, int c0, int c1,
+    double& best_s, int& best_b, int& best_nl) {
+    const int lane = threadIdx.x & 63;
+    int ln[4], l1[4];
+    int tn = 0, t1 = 0;
+    #pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint2 v = counts(lane * 4 + k);
+        ln[k] = (int)v.x;
+        l1[k] = (int)v.y;
+        tn += ln[k];
+        t1 += l1[k];
+    }
+    int cn, c1f;   // exclusive prefix counts of this lane's first bin
+    if (PACKED_SCAN) {
+        const int sc = wave_scan_incl_i32(tn | (t1 << 16));
+        cn = (sc & 0xFFFF) - tn;
+        c1f = (sc >> 16) - t1;
+    } else {
+        cn = wave_scan_incl_i32(tn) - tn;
+        c1f = wave_scan_incl_i32(t1) - t1;
+    }
+    best_s = -1.0;   // all real scores are > 0
+    best_b = -1;
+    best_nl = 0;
+    #pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int b = lane * 4 + k;
+        cn += ln[k];
+        c1f += l1[k];
+        if (ln[k] == 0 || b < bmin || b >= bmax) continue;
+        const double s = split_score(cn, c1f, n, c0, c1);
+        if (s > best_s) { best_s = s; best_b = b; best_nl = cn; }
+    }
+    wave_argmax_mid(best_s, best_b, best_nl);
+}
+
+// The split chosen among a node's candidates.  Candidates are offered in
+// permutation order and a later one must be strictly better, so the first
+// of equal scores is kept; bin < 0 marks a candidate with no valid bin.
+struct BestSplit {
+    double score;
+    int feat, bin, nL;   // feat = -1: no valid split (the node is a leaf)
+};
+__device__ __forceinline__ BestSplit no_split() {
+    return {-1.0e300, -1, -1, 0};
+}
+__device__ __forceinline__ void offer_split(BestSplit& best, double score,
+                                            int feat, int bin, int nL) {
+    if (bin >= 0 && score > best.score) best = {score, feat, bin, nL};
+}
+
+// Turn `node` of `job` (node arrays at nbase) into a split on (feat, bin):
+// allocate its two children (both start as leaves; right = left + 1) and
+// return the left child's id.  Called by one thread.
+__device__ __forceinline__ int commit_split(const ForestDev& a, int job,
+                                            long nbase, int node, int feat,
+                                            int bin) {
+    const int l = atomicAdd(&a.node_alloc[job], 2);
+    a.nfeat[nbase + l] = LEAF_SENTINEL;
+    a.nfeat[nbase + l + 1] = LEAF_SENTINEL;
+    a.nfeat[nbase + node] = feat;
+    a.nsplit[nbase + node] = bin;
+    a.nleft[nbase + node] = l;
+    return l;
+}
+
+// Occupied-bin range [sh_bmin[f], sh_bmax[f]] of every feature's histogram
+// row (total(f, b) = bin count), by the whole block: each thread scans one
+// 16-bin segment of one feature.  Ends with a barrier.
+template <class TotalFn>
+__device__ __forceinline__ void block_bin_ranges(int F, TotalFn total,
+                                                 int* sh_bmin, int* sh_bmax) {
+    const int tid = threadIdx.x;
+    if (tid < F) {
+        sh_bmin[tid] = 256;
+        sh_bmax[tid] = -1;
+    }
+    __syncthreads();
+    const int f = tid >> 4;
+    const int seg = (tid & 15) * 16;
+    if (f < F) {
+        int lo = 256, hi = -1;
+        for (int b = seg; b < seg + 16; ++b)
+            if (total(f, b)) {
+                if (lo == 256) lo = b;
+                hi = b;
+            }
+        if (hi >= 0) {
+            atomicMin(&sh_bmin[f], lo);
+            atomicMax(&sh_bmax[f], hi);
+        }
+    }
+    __syncthreads();
+}
+
+// Feature permutation and candidate walk of a block-built node [s, e):
+// wave 0 keeps the permutation in a register and walks it, taking
+// non-constant features (sh_min[f] != sh_max[f]; a constant one is skipped
+// and not counted) until max_features are found.  Fills sh_cand and, for
+// the random splitter, each candidate's drawn bin in sh_cbin; returns the
+// candidate count to every thread.  The per-feature ranges must be
+// complete (barrier) on entry; ends with a barrier.
+__device__ __forceinline__ int block_candidates(
+    const ForestDev& a, uint32_t key, int depth, int s, int e,
+    int max_features, bool random, const int* sh_min, const int* sh_max,
+    int* sh_cand, int* sh_cbin, int* sh_ncand) {
+    if (threadIdx.x < 64) {
+        const uint64_t perm = featsel_perm(a, key, depth, s, e);
+        const uint32_t thr_mine =
+            random ? thresh_draws(a, key, depth, s, e) : 0u;
+        int nc = 0;
+        for (int i = 0; i < a.F && nc < max_features; ++i) {
+            const int f = perm_at(perm, i);
+            // every lane reads the same word: keep the walk scalar
+            const int mn = __builtin_amdgcn_readfirstlane(sh_min[f]);
+            const int mx = __builtin_amdgcn_readfirstlane(sh_max[f]);
+            if (mn == mx) continue;
+            const int b = random ? et_bin(thr_mine, f, mn, mx) : 0;
+            if (threadIdx.x == 0) {
+                sh_cand[nc] = f;
+                if (random) sh_cbin[nc] = b;
+            }
+            ++nc;
+        }
+        if (threadIdx.x == 0) *sh_ncand = nc;
+    }
+    __syncthreads();
+    return *sh_ncand;
+}
+
+// Stable partition of entries [start, end) by the whole block, 256-wide
+// tiles: load(i, v) fetches entry i into v and returns whether it goes
+// left; store(dst, v) places it.  Lefts are packed from `start`, rights
+// from start + nL, both in source order.  Ranks come from wave ballots
+// (valid lanes are a prefix of the tile, so cross-wave offsets are 4 LDS
+// words); the running offsets are block-uniform and stay in registers.
+// Two barriers per tile, the second after the tile's stores.
+template <class LoadFn, class StoreFn>
+__device__ __forceinline__ void block_partition(
+    int start, int end, int nL, int* sh_wsum, LoadFn load, StoreFn store) {
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    int loff = 0, roff = 0;
+    for (int base = start; base < end; base += HBLK) {
+        const int i = base + tid;
+        const bool valid = i < end;
+        int v = 0;
+        bool left = false;
+        if (valid) left = load(i, v);
+        const unsigned long long lm = __ballot(left);
+        const int left_rank = __popcll(lm & ((1ULL << lane) - 1ULL));
+        if (lane == 0) sh_wsum[wave] = __popcll(lm);
+        __syncthreads();
+        int lefts_before = left_rank;   // in this tile
+        for (int ww = 0; ww < wave; ++ww) lefts_before += sh_wsum[ww];
+        const int tile_left = sh_wsum[0] + sh_wsum[1] + sh_wsum[2]
+                              + sh_wsum[3];
+        const int tile_n = min(HBLK, end - base);
+        if (valid)
+            // rights before me = my tile index - lefts before me
+            store(left ? start + loff + lefts_before
+                       : start + nL + roff + (i - base) - lefts_before, v);
+        __syncthreads();
+        loff += tile_left;
+        roff += tile_n - tile_left;
+    }
+}
+
+// The level kernels' partition: sidx_cur -> sidx_nxt on code(feat) <= bin.
+__device__ __forceinline__ void partition_samples(
+    const ForestDev& a, const WorkItem& it, const BestSplit& best,
+    int* sh_wsum) {
+    const long sbase = a.j_sidx_off[it.job];
+    block_partition(
+        it.start, it.end, best.nL, sh_wsum,
+        [&](int i, int& row) {
+            row = a.sidx_cur[sbase + i];
+            return a.codes[(size_t)row * FPAD + best.feat]
+                   <= (uint32_t)best.bin;
+        },
+        [&](int dst, int row) { a.sidx_nxt[sbase + dst] = row; });
+}
+
 // ---------------------------------------------------------------------------
 // Init: fill per-job sample indices (bootstrap or identity) and root items.
 // Bootstrap draw i: bounded(philox(TAG_BOOTSTRAP, 0, 0, i), n)  — matches
@@ -197,15 +470,13 @@ template <bool WIDE>
 __launch_bounds__(HBLK)
 __global__ void hist_split_kernel(ForestDev a) {
     __shared__ uint32_t hist[FPAD * 256 * (WIDE ? 2 : 1)];
-    __shared__ int sh_scan[HBLK];
+    __shared__ int sh_wsum[HBLK / 64];
     __shared__ int sh_bmin[FPAD], sh_bmax[FPAD];
     __shared__ int sh_cand[FPAD], sh_ncand;
     __shared__ double sh_score[FPAD];
     __shared__ int sh_bin[FPAD], sh_nL[FPAD];
-    __shared__ int sh_bestf, sh_bestbin, sh_bestnL;
-    __shared__ int sh_loff, sh_roff;
+    __shared__ BestSplit sh_best;
     __shared__ int sh_lid;                 // allocated left-child node id
-    __shared__ uint32_t sh_draws[FPAD];
     __shared__ int sh_accum_small;         // phase-8 plan flags
     __shared__ int sh_slot_small, sh_slot_large, sh_small_is_left;
 
@@ -219,7 +490,6 @@ __global__ void hist_split_kernel(ForestDev a) {
         const int n = it.end - it.start;
         if ((n >= 65536) != WIDE) continue;   // size-class filter (uniform)
         if (a.j_rand[it.job]) continue;       // random-splitter: et_split's
-        const int max_features = a.j_mf[it.job];
         const long sbase = a.j_sidx_off[it.job];
         const long nbase = a.j_node_off[it.job];
         const uint32_t key = (uint32_t)a.j_key[it.job];
@@ -266,17 +536,9 @@ __global__ void hist_split_kernel(ForestDev a) {
         }
         __syncthreads();
 
-        // Phase 2: class counts from feature-0 histogram (wave reduce +
-        // one cross-wave combine: 1 barrier instead of 8).
-        {
-            int v = (int)h_1(0, tid);
-            for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
-            if (lane == 0) sh_scan[wave] = v;
-        }
-        __syncthreads();
-        const int c1 = sh_scan[0] + sh_scan[1] + sh_scan[2] + sh_scan[3];
+        // Phase 2: class counts from the feature-0 histogram.
+        const int c1 = block_sum_i32((int)h_1(0, tid), sh_wsum);
         const int c0 = n - c1;
-        __syncthreads();
 
         if (tid == 0) {
             a.ncnt0[nbase + it.node] = (float)c0;
@@ -288,142 +550,27 @@ __global__ void hist_split_kernel(ForestDev a) {
             continue;  // leaf (nfeat stays LEAF_SENTINEL)
         }
 
-        // Phase 3: occupied-bin range per feature (parallel: each of the
-        // 256 threads scans one 16-bin segment of one feature).
-        if (tid < F) {
-            sh_bmin[tid] = 256;
-            sh_bmax[tid] = -1;
-        }
-        __syncthreads();
-        {
-            const int f3 = tid >> 4;
-            const int seg = (tid & 15) * 16;
-            if (f3 < F) {
-                int lo = 256, hi = -1;
-                for (int b = seg; b < seg + 16; ++b)
-                    if (h_n(f3, b)) {
-                        if (lo == 256) lo = b;
-                        hi = b;
-                    }
-                if (hi >= 0) {
-                    atomicMin(&sh_bmin[f3], lo);
-                    atomicMax(&sh_bmax[f3], hi);
-                }
-            }
-        }
-        __syncthreads();
+        // Phase 3: occupied-bin range per feature.
+        block_bin_ranges(F, h_n, sh_bmin, sh_bmax);
 
-        // Phase 4: feature permutation (partial Fisher-Yates, counters
-        // (TAG_FEATSEL|depth<<8, start, end, i)) — draws computed by the
-        // first F-1 threads in parallel, swap walk on thread 0 — and the
-        // candidate list: walk perm, non-constant until max_features.
-        if (tid < FPAD)
-            sh_draws[tid] = philox_draw(
-                TAG_FEATSEL | ((uint32_t)(it.depth & 0xFF) << 8),
-                (uint32_t)it.start, (uint32_t)it.end, (uint32_t)tid,
-                a.seed, key);
-        __syncthreads();
-        if (tid == 0) {
-            int perm[FPAD];
-            for (int f = 0; f < F; ++f) perm[f] = f;
-            for (int i = 0; i < F - 1; ++i) {
-                int j = i + (int)philox_bounded(sh_draws[i],
-                                                (uint32_t)(F - i));
-                int t = perm[i]; perm[i] = perm[j]; perm[j] = t;
-            }
-            int nc = 0;
-            for (int i = 0; i < F && nc < max_features; ++i) {
-                int f = perm[i];
-                if (sh_bmin[f] != sh_bmax[f]) sh_cand[nc++] = f;
-            }
-            sh_ncand = nc;
-        }
-        __syncthreads();
-
-        const int ncand = sh_ncand;
+        // Phase 4: feature permutation + candidate list.
+        const int ncand = block_candidates(
+            a, key, it.depth, it.start, it.end, a.j_mf[it.job], false,
+            sh_bmin, sh_bmax, sh_cand, nullptr, &sh_ncand);
         if (ncand == 0) {
             __syncthreads();
             continue;  // all features constant: leaf
         }
 
         // Phase 5: evaluate candidates; wave w handles candidates w, w+4, ...
-        // Scores in fp64, expression order matching the reference
-        // (-ffp-contract=off).
+        // (two 32-bit scans: WIDE counts do not fit the packed one).
         for (int ci = wave; ci < ncand; ci += HBLK / 64) {
             const int f = sh_cand[ci];
-            const int bmin = sh_bmin[f], bmax = sh_bmax[f];
-
-            // Per-lane 4-bin partial sums, then wave-inclusive scan.
-            int ln[4], l1[4];
-            int tn = 0, t1 = 0;
-            for (int k = 0; k < 4; ++k) {
-                int b = lane * 4 + k;
-                ln[k] = (int)h_n(f, b);
-                l1[k] = (int)h_1(f, b);
-                tn += ln[k];
-                t1 += l1[k];
-            }
-            int scn = tn, sc1 = t1;
-            for (int d = 1; d < 64; d <<= 1) {
-                int un = __shfl_up(scn, d);
-                int u1 = __shfl_up(sc1, d);
-                if (lane >= d) { scn += un; sc1 += u1; }
-            }
-            const int excl_n = scn - tn, excl_1 = sc1 - t1;
-
-            double best_s = -1.0;  // all real scores are > 0
-            int best_b = -1, best_nl = 0;
-
-            if (a.j_rand[it.job]) {
-                uint32_t tag = TAG_THRESH | ((uint32_t)(it.depth & 0xFF) << 8);
-                uint32_t u = philox_draw(tag, (uint32_t)it.start,
-                                         (uint32_t)it.end, (uint32_t)f,
-                                         a.seed, key);
-                int b = bmin + (int)philox_bounded(u, (uint32_t)(bmax - bmin));
-                // the lane owning bin b evaluates it
-                if (b >= lane * 4 && b < lane * 4 + 4) {
-                    int cn = excl_n, c1f = excl_1;
-                    for (int k = 0; k <= b - lane * 4; ++k) {
-                        cn += ln[k];
-                        c1f += l1[k];
-                    }
-                    long nL = cn, n1L = c1f;
-                    long n0L = nL - n1L, nR = n - nL;
-                    long n1R = c1 - n1L, n0R = c0 - n0L;
-                    best_s = (double)(n0L * n0L + n1L * n1L) / (double)nL
-                           + (double)(n0R * n0R + n1R * n1R) / (double)nR;
-                    best_b = b;
-                    best_nl = (int)nL;
-                }
-            } else {
-                int cn = excl_n, c1f = excl_1;
-                for (int k = 0; k < 4; ++k) {
-                    int b = lane * 4 + k;
-                    cn += ln[k];
-                    c1f += l1[k];
-                    // split scores only change at occupied bins, and the
-                    // first bin of an equal-score run is occupied, so
-                    // skipping empty bins preserves the argmax-first result
-                    if (ln[k] == 0 || b < bmin || b >= bmax) continue;
-                    long nL = cn, n1L = c1f;
-                    long n0L = nL - n1L, nR = n - nL;
-                    long n1R = c1 - n1L, n0R = c0 - n0L;
-                    double s = (double)(n0L * n0L + n1L * n1L) / (double)nL
-                             + (double)(n0R * n0R + n1R * n1R) / (double)nR;
-                    if (s > best_s) { best_s = s; best_b = b; best_nl = (int)nL; }
-                }
-            }
-
-            // Wave arg-max with first-of-ties (lowest bin) tie-break.
-            for (int d = 32; d > 0; d >>= 1) {
-                double os = __shfl_down(best_s, d);
-                int ob = __shfl_down(best_b, d);
-                int onl = __shfl_down(best_nl, d);
-                if (os > best_s || (os == best_s && ob != -1 &&
-                                    (best_b == -1 || ob < best_b))) {
-                    best_s = os; best_b = ob; best_nl = onl;
-                }
-            }
+            double best_s;
+            int best_b, best_nl;
+            wave_best_bin<false>(
+                [&](int b) { return uint2{h_n(f, b), h_1(f, b)}; },
+                sh_bmin[f], sh_bmax[f], n, c0, c1, best_s, best_b, best_nl);
             if (lane == 0) {
                 sh_score[ci] = best_s;
                 sh_bin[ci] = best_b;
@@ -432,87 +579,28 @@ __global__ void hist_split_kernel(ForestDev a) {
         }
         __syncthreads();
 
-        // Phase 6 (thread 0): sequential select in perm order, strict >.
+        // Phase 6 (thread 0): select in permutation order and commit.
         if (tid == 0) {
-            double best_s = -1.0e300;
-            int bf = -1, bb = -1, bnl = 0;
-            for (int ci = 0; ci < ncand; ++ci) {
-                if (sh_bin[ci] >= 0 && sh_score[ci] > best_s) {
-                    best_s = sh_score[ci];
-                    bf = sh_cand[ci];
-                    bb = sh_bin[ci];
-                    bnl = sh_nL[ci];
-                }
-            }
-            sh_bestf = bf;
-            sh_bestbin = bb;
-            sh_bestnL = bnl;
-            if (bf >= 0) {
-                int l = atomicAdd(&a.node_alloc[it.job], 2);
-                a.nfeat[nbase + l] = LEAF_SENTINEL;       // children start
-                a.nfeat[nbase + l + 1] = LEAF_SENTINEL;   // as leaves
-                a.nfeat[nbase + it.node] = bf;
-                a.nsplit[nbase + it.node] = bb;
-                a.nleft[nbase + it.node] = l;
-                sh_lid = l;
-            }
-            sh_loff = 0;
-            sh_roff = 0;
+            BestSplit best = no_split();
+            for (int ci = 0; ci < ncand; ++ci)
+                offer_split(best, sh_score[ci], sh_cand[ci], sh_bin[ci],
+                            sh_nL[ci]);
+            sh_best = best;
+            if (best.feat >= 0)
+                sh_lid = commit_split(a, it.job, nbase, it.node, best.feat,
+                                      best.bin);
         }
         __syncthreads();
 
-        const int bf = sh_bestf;
-        if (bf < 0) {
+        const BestSplit best = sh_best;
+        if (best.feat < 0) {
             __syncthreads();
             continue;  // no valid split: leaf
         }
-        const int bb = sh_bestbin;
-        const int nL = sh_bestnL;
+        const int bf = best.feat, bb = best.bin, nL = best.nL;
 
-        // Phase 7: stable partition into sidx_nxt, 256-wide tiles.
-        // Ranks come from wave ballots (valid lanes are a prefix of the
-        // tile, so cross-wave offsets are 4 LDS words): 2 barriers per
-        // tile instead of 16.
-        for (int base = it.start; base < it.end; base += HBLK) {
-            const int i = base + tid;
-            const bool valid = i < it.end;
-            int row = 0, flag = 0;
-            if (valid) {
-                row = a.sidx_cur[sbase + i];
-                uint32_t b = a.codes[(size_t)row * FPAD + bf];
-                flag = (int)(b <= (uint32_t)bb);
-            }
-            const unsigned long long lm = __ballot(valid && flag);
-            const unsigned long long below = (1ULL << lane) - 1ULL;
-            const int left_rank = __popcll(lm & below);
-            const int wave_left = __popcll(lm);
-            if (lane == 0) sh_scan[wave] = wave_left;
-            __syncthreads();
-            int wave_left_excl = 0;
-            for (int ww = 0; ww < wave; ++ww)
-                wave_left_excl += sh_scan[ww];
-            const int tile_left = sh_scan[0] + sh_scan[1] + sh_scan[2]
-                                  + sh_scan[3];
-            const int tile_n = min(HBLK, it.end - base);
-            if (valid) {
-                if (flag) {
-                    a.sidx_nxt[sbase + it.start + sh_loff + wave_left_excl
-                               + left_rank] = row;
-                } else {
-                    // rights before me = my tile index - lefts before me
-                    const int rights_before =
-                        (i - base) - (wave_left_excl + left_rank);
-                    a.sidx_nxt[sbase + it.start + nL + sh_roff
-                               + rights_before] = row;
-                }
-            }
-            __syncthreads();
-            if (tid == 0) {
-                sh_loff += tile_left;
-                sh_roff += tile_n - tile_left;
-            }
-            __syncthreads();
-        }
+        // Phase 7: stable partition into sidx_nxt.
+        partition_samples(a, it, best, sh_wsum);
 
         // Phase 8: histogram-subtraction bookkeeping + child item push.
         // A big splitting node accumulates its SMALLER child's histogram
@@ -620,13 +708,12 @@ __global__ void hist_split_kernel(ForestDev a) {
 // ---------------------------------------------------------------------------
 __launch_bounds__(HBLK)
 __global__ void et_split_kernel(ForestDev a) {
-    __shared__ int sh_scan[HBLK];
+    __shared__ int sh_wsum[HBLK / 64];
     __shared__ int sh_min[FPAD], sh_max[FPAD];
     __shared__ int sh_cand[FPAD], sh_cbin[FPAD], sh_ncand;
-    __shared__ uint32_t sh_draws[FPAD], sh_tdraws[FPAD];
     __shared__ int sh_cnt[4][FPAD], sh_cnt1[4][FPAD];
-    __shared__ int sh_bestf, sh_bestbin, sh_bestnL;
-    __shared__ int sh_loff, sh_roff, sh_lid;
+    __shared__ BestSplit sh_best;
+    __shared__ int sh_lid;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -637,7 +724,6 @@ __global__ void et_split_kernel(ForestDev a) {
         WorkItem it = a.cur[wi];
         const int n = it.end - it.start;
         if (!a.j_rand[it.job]) continue;     // best-splitter: hist_split's
-        const int max_features = a.j_mf[it.job];
         const long sbase = a.j_sidx_off[it.job];
         const long nbase = a.j_node_off[it.job];
         const uint32_t key = (uint32_t)a.j_key[it.job];
@@ -666,23 +752,17 @@ __global__ void et_split_kernel(ForestDev a) {
                 lmax[f] = max(lmax[f], b);
             }
         }
-        for (int d = 32; d > 0; d >>= 1) lc1 += __shfl_down(lc1, d);
-        if (lane == 0) sh_scan[wave] = lc1;
         for (int f = 0; f < F; ++f) {
-            int mn = lmin[f], mx = lmax[f];
-            for (int d = 32; d > 0; d >>= 1) {
-                mn = min(mn, __shfl_xor(mn, d));
-                mx = max(mx, __shfl_xor(mx, d));
-            }
+            const int mn = wave_min_i32(lmin[f]);
+            const int mx = wave_max_i32(lmax[f]);
             if (lane == 0) {
                 atomicMin(&sh_min[f], mn);
                 atomicMax(&sh_max[f], mx);
             }
         }
-        __syncthreads();
-        const int c1 = sh_scan[0] + sh_scan[1] + sh_scan[2] + sh_scan[3];
+        // (its barriers also complete sh_min / sh_max)
+        const int c1 = block_sum_i32(lc1, sh_wsum);
         const int c0 = n - c1;
-        __syncthreads();
 
         if (tid == 0) {
             a.ncnt0[nbase + it.node] = (float)c0;
@@ -693,41 +773,10 @@ __global__ void et_split_kernel(ForestDev a) {
             continue;
         }
 
-        // Permutation walk + threshold draws: all Philox draws computed
-        // by the first F threads in parallel, walk on thread 0.
-        if (tid < FPAD) {
-            sh_draws[tid] = philox_draw(
-                TAG_FEATSEL | ((uint32_t)(it.depth & 0xFF) << 8),
-                (uint32_t)it.start, (uint32_t)it.end, (uint32_t)tid,
-                a.seed, key);
-            sh_tdraws[tid] = philox_draw(
-                TAG_THRESH | ((uint32_t)(it.depth & 0xFF) << 8),
-                (uint32_t)it.start, (uint32_t)it.end, (uint32_t)tid,
-                a.seed, key);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            int perm[FPAD];
-            for (int f = 0; f < F; ++f) perm[f] = f;
-            for (int i = 0; i < F - 1; ++i) {
-                int j = i + (int)philox_bounded(sh_draws[i],
-                                                (uint32_t)(F - i));
-                int t = perm[i]; perm[i] = perm[j]; perm[j] = t;
-            }
-            int nc = 0;
-            for (int i = 0; i < F && nc < max_features; ++i) {
-                int f = perm[i];
-                if (sh_min[f] == sh_max[f]) continue;
-                sh_cand[nc] = f;
-                sh_cbin[nc] = sh_min[f] + (int)philox_bounded(
-                    sh_tdraws[f], (uint32_t)(sh_max[f] - sh_min[f]));
-                ++nc;
-            }
-            sh_ncand = nc;
-        }
-        __syncthreads();
-
-        const int ncand = sh_ncand;
+        // Feature permutation, candidate list and each candidate's drawn bin.
+        const int ncand = block_candidates(
+            a, key, it.depth, it.start, it.end, a.j_mf[it.job], true,
+            sh_min, sh_max, sh_cand, sh_cbin, &sh_ncand);
         if (ncand == 0) {
             __syncthreads();
             continue;
@@ -751,11 +800,8 @@ __global__ void et_split_kernel(ForestDev a) {
             }
         }
         for (int ci = 0; ci < ncand; ++ci) {
-            int c = cnt[ci], c1l = cnt1[ci];
-            for (int d = 32; d > 0; d >>= 1) {
-                c += __shfl_down(c, d);
-                c1l += __shfl_down(c1l, d);
-            }
+            const int c = wave_sum_i32(cnt[ci]);
+            const int c1l = wave_sum_i32(cnt1[ci]);
             if (lane == 0) {
                 sh_cnt[wave][ci] = c;
                 sh_cnt1[wave][ci] = c1l;
@@ -763,366 +809,35 @@ __global__ void et_split_kernel(ForestDev a) {
         }
         __syncthreads();
 
-        // Select (thread 0): candidates in perm order, strict >.
+        // Select in permutation order and commit (thread 0).
         if (tid == 0) {
-            double best_s = -1.0e300;
-            int bf = -1, bb = -1, bnl = 0;
+            BestSplit best = no_split();
             for (int ci = 0; ci < ncand; ++ci) {
                 const long nL = sh_cnt[0][ci] + sh_cnt[1][ci]
                                 + sh_cnt[2][ci] + sh_cnt[3][ci];
                 const long n1L = sh_cnt1[0][ci] + sh_cnt1[1][ci]
                                  + sh_cnt1[2][ci] + sh_cnt1[3][ci];
-                const long n0L = nL - n1L, nR = n - nL;
-                const long n1R = c1 - n1L, n0R = c0 - n0L;
-                if (nL == 0 || nR == 0) continue;
-                double sc = (double)(n0L * n0L + n1L * n1L) / (double)nL
-                            + (double)(n0R * n0R + n1R * n1R) / (double)nR;
-                if (sc > best_s) {
-                    best_s = sc;
-                    bf = sh_cand[ci];
-                    bb = sh_cbin[ci];
-                    bnl = (int)nL;
-                }
+                if (nL == 0 || nL == n) continue;
+                offer_split(best, split_score(nL, n1L, n, c0, c1),
+                            sh_cand[ci], sh_cbin[ci], (int)nL);
             }
-            sh_bestf = bf;
-            sh_bestbin = bb;
-            sh_bestnL = bnl;
-            if (bf >= 0) {
-                int l = atomicAdd(&a.node_alloc[it.job], 2);
-                a.nfeat[nbase + l] = LEAF_SENTINEL;       // children start
-                a.nfeat[nbase + l + 1] = LEAF_SENTINEL;   // as leaves
-                a.nfeat[nbase + it.node] = bf;
-                a.nsplit[nbase + it.node] = bb;
-                a.nleft[nbase + it.node] = l;
-                sh_lid = l;
-            }
-            sh_loff = 0;
-            sh_roff = 0;
+            sh_best = best;
+            if (best.feat >= 0)
+                sh_lid = commit_split(a, it.job, nbase, it.node, best.feat,
+                                      best.bin);
         }
         __syncthreads();
 
-        const int bf = sh_bestf;
-        if (bf < 0) {
+        const BestSplit best = sh_best;
+        if (best.feat < 0) {
             __syncthreads();
             continue;
         }
-        const int bb = sh_bestbin;
-        const int nL = sh_bestnL;
+        const int nL = best.nL;
 
-        // Partition (same scheme as hist_split_kernel phase 7).
-        for (int base = it.start; base < it.end; base += HBLK) {
-            const int i = base + tid;
-            const bool valid = i < it.end;
-            int row = 0, flag = 0;
-            if (valid) {
-                row = a.sidx_cur[sbase + i];
-                uint32_t b = a.codes[(size_t)row * FPAD + bf];
-                flag = (int)(b <= (uint32_t)bb);
-            }
-            const unsigned long long lm = __ballot(valid && flag);
-            const unsigned long long below = (1ULL << lane) - 1ULL;
-            const int left_rank = __popcll(lm & below);
-            if (lane == 0) sh_scan[wave] = __popcll(lm);
-            __syncthreads();
-            int wave_left_excl = 0;
-            for (int ww = 0; ww < wave; ++ww)
-                wave_left_excl += sh_scan[ww];
-            const int tile_left = sh_scan[0] + sh_scan[1] + sh_scan[2]
-                                  + sh_scan[3];
-            const int tile_n = min(HBLK, it.end - base);
-            if (valid) {
-                if (flag)
-                    a.sidx_nxt[sbase + it.start + sh_loff + wave_left_excl
-                               + left_rank] = row;
-                else
-                    a.sidx_nxt[sbase + it.start + nL + sh_roff
-                               + (i - base) - (wave_left_excl + left_rank)]
-                        = row;
-            }
-            __syncthreads();
-            if (tid == 0) {
-                sh_loff += tile_left;
-                sh_roff += tile_n - tile_left;
-            }
-            __syncthreads();
-        }
+        partition_samples(a, it, best, sh_wsum);
 
         // Push children (no histogram slots on the ET path).
-        if (tid == 0) {
-            route_child(a, {it.job, sh_lid, it.start, it.start + nL,
-                            it.depth + 1, -1});
-            route_child(a, {it.job, sh_lid + 1, it.start + nL, it.end,
-                            it.depth + 1, -1});
-        }
-        __syncthreads();
-    }
-}
-
-// ---------------------------------------------------------------------------
-// Candidate-only Random-Forest level kernel.
-//
-// RF evaluates max_features (= sqrt(F) ~ 4) candidate features per node,
-// but the generic histogram kernel accumulates all 16.  Here pass 1
-// computes per-feature min/max (constancy) + class counts; the Fisher-
-// Yates walk then fixes the <= max_features candidates, and pass 2
-// histograms ONLY those (~4 LDS atomics per sample instead of 16).
-// Split scores, tie-breaks and partition are identical to
-// hist_split_kernel, so trees are unchanged.  No histogram-subtraction
-// pools on this path (children of other candidates are useless to them).
-// ---------------------------------------------------------------------------
-__launch_bounds__(HBLK)
-__global__ void rf_cand_split_kernel(ForestDev a) {
-    __shared__ uint32_t hist[FPAD * 256];   // rows = candidate index
-    __shared__ int sh_scan[HBLK];
-    __shared__ int sh_min[FPAD], sh_max[FPAD];
-    __shared__ int sh_cand[FPAD], sh_ncand;
-    __shared__ uint32_t sh_draws[FPAD];
-    __shared__ double sh_score[FPAD];
-    __shared__ int sh_bin[FPAD], sh_nL[FPAD];
-    __shared__ int sh_bestf, sh_bestbin, sh_bestnL;
-    __shared__ int sh_loff, sh_roff, sh_lid;
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int n_items = *a.cur_count;
-
-    for (int wi = blockIdx.x; wi < n_items; wi += gridDim.x) {
-        WorkItem it = a.cur[wi];
-        const int n = it.end - it.start;
-        if (a.j_rand[it.job]) continue;      // random-splitter: et_split's
-        const int max_features = a.j_mf[it.job];
-        const long sbase = a.j_sidx_off[it.job];
-        const long nbase = a.j_node_off[it.job];
-        const uint32_t key = (uint32_t)a.j_key[it.job];
-        const int F = a.F;
-
-        if (tid < F) {
-            sh_min[tid] = 256;
-            sh_max[tid] = -1;
-        }
-        __syncthreads();
-
-        // Pass 1: per-feature min/max + class-1 count.
-        int lmin[FPAD], lmax[FPAD];
-        #pragma unroll
-        for (int f = 0; f < FPAD; ++f) { lmin[f] = 256; lmax[f] = -1; }
-        int lc1 = 0;
-        for (int i = it.start + tid; i < it.end; i += HBLK) {
-            int row = a.sidx_cur[sbase + i];
-            uint4 cw = *reinterpret_cast<const uint4*>(
-                a.codes + (size_t)row * FPAD);
-            uint32_t w[4] = {cw.x, cw.y, cw.z, cw.w};
-            lc1 += a.labels[row];
-            for (int f = 0; f < F; ++f) {
-                const int b = (int)((w[f >> 2] >> ((f & 3) * 8)) & 0xFFu);
-                lmin[f] = min(lmin[f], b);
-                lmax[f] = max(lmax[f], b);
-            }
-        }
-        for (int d = 32; d > 0; d >>= 1) lc1 += __shfl_down(lc1, d);
-        if (lane == 0) sh_scan[wave] = lc1;
-        for (int f = 0; f < F; ++f) {
-            int mn = lmin[f], mx = lmax[f];
-            for (int d = 32; d > 0; d >>= 1) {
-                mn = min(mn, __shfl_xor(mn, d));
-                mx = max(mx, __shfl_xor(mx, d));
-            }
-            if (lane == 0) {
-                atomicMin(&sh_min[f], mn);
-                atomicMax(&sh_max[f], mx);
-            }
-        }
-        __syncthreads();
-        const int c1 = sh_scan[0] + sh_scan[1] + sh_scan[2] + sh_scan[3];
-        const int c0 = n - c1;
-        __syncthreads();
-
-        if (tid == 0) {
-            a.ncnt0[nbase + it.node] = (float)c0;
-            a.ncnt1[nbase + it.node] = (float)c1;
-        }
-        if (n < 2 || c0 == 0 || c1 == 0) {
-            __syncthreads();
-            continue;
-        }
-
-        // Candidate walk: parallel draws, thread-0 swap walk (same
-        // permutation/constancy semantics as the histogram path).
-        if (tid < FPAD)
-            sh_draws[tid] = philox_draw(
-                TAG_FEATSEL | ((uint32_t)(it.depth & 0xFF) << 8),
-                (uint32_t)it.start, (uint32_t)it.end, (uint32_t)tid,
-                a.seed, key);
-        __syncthreads();
-        if (tid == 0) {
-            int perm[FPAD];
-            for (int f = 0; f < F; ++f) perm[f] = f;
-            for (int i = 0; i < F - 1; ++i) {
-                int j = i + (int)philox_bounded(sh_draws[i],
-                                                (uint32_t)(F - i));
-                int t = perm[i]; perm[i] = perm[j]; perm[j] = t;
-            }
-            int nc = 0;
-            for (int i = 0; i < F && nc < max_features; ++i) {
-                int f = perm[i];
-                if (sh_min[f] != sh_max[f]) sh_cand[nc++] = f;
-            }
-            sh_ncand = nc;
-        }
-        __syncthreads();
-
-        const int ncand = sh_ncand;
-        if (ncand == 0) {
-            __syncthreads();
-            continue;
-        }
-
-        // Pass 2: packed histograms of the candidate features only.
-        for (int i = tid; i < ncand * 256; i += HBLK) hist[i] = 0;
-        __syncthreads();
-        for (int i = it.start + tid; i < it.end; i += HBLK) {
-            int row = a.sidx_cur[sbase + i];
-            uint4 cw = *reinterpret_cast<const uint4*>(
-                a.codes + (size_t)row * FPAD);
-            uint32_t w[4] = {cw.x, cw.y, cw.z, cw.w};
-            const uint32_t inc = 1u | ((uint32_t)a.labels[row] << 16);
-            for (int ci = 0; ci < ncand; ++ci) {
-                const int f = sh_cand[ci];
-                uint32_t b = (w[f >> 2] >> ((f & 3) * 8)) & 0xFFu;
-                atomicAdd(&hist[ci * 256 + b], inc);
-            }
-        }
-        __syncthreads();
-
-        // Evaluate: wave w handles candidates w, w+4, ... (identical fp64
-        // scores and tie-breaks to hist_split_kernel phase 5).
-        for (int ci = wave; ci < ncand; ci += HBLK / 64) {
-            const int f = sh_cand[ci];
-            const int bmin = sh_min[f], bmax = sh_max[f];
-            int ln[4], l1[4];
-            int tn = 0, t1 = 0;
-            for (int k = 0; k < 4; ++k) {
-                uint32_t v = hist[ci * 256 + lane * 4 + k];
-                ln[k] = (int)(v & 0xFFFFu);
-                l1[k] = (int)(v >> 16);
-                tn += ln[k];
-                t1 += l1[k];
-            }
-            int scn = tn, sc1 = t1;
-            for (int d = 1; d < 64; d <<= 1) {
-                int un = __shfl_up(scn, d);
-                int u1 = __shfl_up(sc1, d);
-                if (lane >= d) { scn += un; sc1 += u1; }
-            }
-            const int excl_n = scn - tn, excl_1 = sc1 - t1;
-
-            double best_s = -1.0;
-            int best_b = -1, best_nl = 0;
-            int cn = excl_n, c1f = excl_1;
-            for (int k = 0; k < 4; ++k) {
-                int b = lane * 4 + k;
-                cn += ln[k];
-                c1f += l1[k];
-                if (ln[k] == 0 || b < bmin || b >= bmax) continue;
-                long nL = cn, n1L = c1f;
-                long n0L = nL - n1L, nR = n - nL;
-                long n1R = c1 - n1L, n0R = c0 - n0L;
-                double s = (double)(n0L * n0L + n1L * n1L) / (double)nL
-                         + (double)(n0R * n0R + n1R * n1R) / (double)nR;
-                if (s > best_s) { best_s = s; best_b = b; best_nl = (int)nL; }
-            }
-            for (int d = 32; d > 0; d >>= 1) {
-                double os = __shfl_down(best_s, d);
-                int ob = __shfl_down(best_b, d);
-                int onl = __shfl_down(best_nl, d);
-                if (os > best_s || (os == best_s && ob != -1 &&
-                                    (best_b == -1 || ob < best_b))) {
-                    best_s = os; best_b = ob; best_nl = onl;
-                }
-            }
-            if (lane == 0) {
-                sh_score[ci] = best_s;
-                sh_bin[ci] = best_b;
-                sh_nL[ci] = best_nl;
-            }
-        }
-        __syncthreads();
-
-        if (tid == 0) {
-            double best_s = -1.0e300;
-            int bf = -1, bb = -1, bnl = 0;
-            for (int ci = 0; ci < ncand; ++ci) {
-                if (sh_bin[ci] >= 0 && sh_score[ci] > best_s) {
-                    best_s = sh_score[ci];
-                    bf = sh_cand[ci];
-                    bb = sh_bin[ci];
-                    bnl = sh_nL[ci];
-                }
-            }
-            sh_bestf = bf;
-            sh_bestbin = bb;
-            sh_bestnL = bnl;
-            if (bf >= 0) {
-                int l = atomicAdd(&a.node_alloc[it.job], 2);
-                a.nfeat[nbase + l] = LEAF_SENTINEL;       // children start
-                a.nfeat[nbase + l + 1] = LEAF_SENTINEL;   // as leaves
-                a.nfeat[nbase + it.node] = bf;
-                a.nsplit[nbase + it.node] = bb;
-                a.nleft[nbase + it.node] = l;
-                sh_lid = l;
-            }
-            sh_loff = 0;
-            sh_roff = 0;
-        }
-        __syncthreads();
-
-        const int bf = sh_bestf;
-        if (bf < 0) {
-            __syncthreads();
-            continue;
-        }
-        const int bb = sh_bestbin;
-        const int nL = sh_bestnL;
-
-        // Partition (identical to hist_split_kernel phase 7).
-        for (int base = it.start; base < it.end; base += HBLK) {
-            const int i = base + tid;
-            const bool valid = i < it.end;
-            int row = 0, flag = 0;
-            if (valid) {
-                row = a.sidx_cur[sbase + i];
-                uint32_t b = a.codes[(size_t)row * FPAD + bf];
-                flag = (int)(b <= (uint32_t)bb);
-            }
-            const unsigned long long lm = __ballot(valid && flag);
-            const unsigned long long below = (1ULL << lane) - 1ULL;
-            const int left_rank = __popcll(lm & below);
-            if (lane == 0) sh_scan[wave] = __popcll(lm);
-            __syncthreads();
-            int wave_left_excl = 0;
-            for (int ww = 0; ww < wave; ++ww)
-                wave_left_excl += sh_scan[ww];
-            const int tile_left = sh_scan[0] + sh_scan[1] + sh_scan[2]
-                                  + sh_scan[3];
-            const int tile_n = min(HBLK, it.end - base);
-            if (valid) {
-                if (flag)
-                    a.sidx_nxt[sbase + it.start + sh_loff + wave_left_excl
-                               + left_rank] = row;
-                else
-                    a.sidx_nxt[sbase + it.start + nL + sh_roff
-                               + (i - base) - (wave_left_excl + left_rank)]
-                        = row;
-            }
-            __syncthreads();
-            if (tid == 0) {
-                sh_loff += tile_left;
-                sh_roff += tile_n - tile_left;
-            }
-            __syncthreads();
-        }
-
         if (tid == 0) {
             route_child(a, {it.job, sh_lid, it.start, it.start + nL,
                             it.depth + 1, -1});
@@ -1181,15 +896,6 @@ __device__ __forceinline__ void mid_farm_small(
                       it.hist_slot};
     else
         atomicExch(a.err_flag, 1);
-}
-
-// Code of feature f from a 16-byte row.  Selects instead of indexing: a
-// dynamically indexed private array is promoted to LDS (or scratch) by
-// the compiler, which puts a store + load round trip on every sample.
-__device__ __forceinline__ uint32_t code_byte(const uint4& cw, int f) {
-    const int k = f >> 2;
-    const uint32_t w = k == 0 ? cw.x : k == 1 ? cw.y : k == 2 ? cw.z : cw.w;
-    return (w >> ((f & 3) * 8)) & 0xFFu;
 }
 
 // One 64-lane wave splits one node [ls, le) of the staged window and
@@ -1281,17 +987,9 @@ __device__ __forceinline__ void mid_wave_node(
     // Feature permutation + candidate walk, wave-uniform in registers:
     // candidates, their ranges and (ET) drawn bins are packed 4 / 8 bits
     // per candidate (WAVE_CANDS = 4 candidates, values <= 255).
-    const uint64_t perm = feature_perm(
-        philox_draw(TAG_FEATSEL | ((uint32_t)(depth & 0xFF) << 8),
-                    (uint32_t)gs, (uint32_t)ge,
-                    (uint32_t)(lane < FPAD ? lane : 0), a.seed, key),
-        F);
-    uint32_t thr_mine = 0;
-    if (splitter_random)
-        thr_mine = philox_draw(
-            TAG_THRESH | ((uint32_t)(depth & 0xFF) << 8),
-            (uint32_t)gs, (uint32_t)ge,
-            (uint32_t)(lane < FPAD ? lane : 0), a.seed, key);
+    const uint64_t perm = featsel_perm(a, key, depth, gs, ge);
+    const uint32_t thr_mine =
+        splitter_random ? thresh_draws(a, key, depth, gs, ge) : 0u;
     int ncand = 0;
     uint32_t cand_pk = 0, cbin_pk = 0, cmin_pk = 0, cmax_pk = 0;
     for (int i = 0; i < F && ncand < max_features; ++i) {
@@ -1303,15 +1001,12 @@ __device__ __forceinline__ void mid_wave_node(
         cmin_pk |= (uint32_t)mn << (8 * ncand);
         cmax_pk |= (uint32_t)mx << (8 * ncand);
         if (splitter_random)
-            cbin_pk |= (uint32_t)(mn + (int)philox_bounded(
-                wave_bcast(thr_mine, f), (uint32_t)(mx - mn)))
-                       << (8 * ncand);
+            cbin_pk |= (uint32_t)et_bin(thr_mine, f, mn, mx) << (8 * ncand);
         ++ncand;
     }
     if (ncand == 0) return;   // all candidates constant: leaf
 
-    double best_s = -1.0e300;
-    int bf = -1, bb = -1, bnl = 0;
+    BestSplit best = no_split();
 
     if (splitter_random) {
         // ET: counts at each candidate's drawn bin — histogram-free.  The
@@ -1335,19 +1030,12 @@ __device__ __forceinline__ void mid_wave_node(
         #pragma unroll
         for (int ci = 0; ci < WAVE_CANDS; ++ci) {
             if (ci >= ncand) break;
-            const int tot = wave_sum_i32(cnt[ci]);
-            const long nL = tot & 0xFFFF, n1L = tot >> 16;
-            const long n0L = nL - n1L, nR = n - nL;
-            const long n1R = c1 - n1L, n0R = c0 - n0L;
-            if (nL == 0 || nR == 0) continue;
-            const double sc = (double)(n0L * n0L + n1L * n1L) / (double)nL
-                            + (double)(n0R * n0R + n1R * n1R) / (double)nR;
-            if (sc > best_s) {
-                best_s = sc;
-                bf = (int)((cand_pk >> (4 * ci)) & 15u);
-                bb = (int)((cbin_pk >> (8 * ci)) & 0xFFu);
-                bnl = (int)nL;
-            }
+            const uint2 t = unpack_counts((uint32_t)wave_sum_i32(cnt[ci]));
+            const int nL = (int)t.x;
+            if (nL == 0 || nL == n) continue;
+            offer_split(best, split_score(nL, t.y, n, c0, c1),
+                        (int)((cand_pk >> (4 * ci)) & 15u),
+                        (int)((cbin_pk >> (8 * ci)) & 0xFFu), nL);
         }
     } else {
         // RF: candidate-only packed LDS histograms.
@@ -1365,60 +1053,23 @@ __device__ __forceinline__ void mid_wave_node(
             }
         }
         for (int ci = 0; ci < ncand; ++ci) {
-            const int bmin = (int)((cmin_pk >> (8 * ci)) & 0xFFu);
-            const int bmax = (int)((cmax_pk >> (8 * ci)) & 0xFFu);
-            int ln[4], l1[4];
-            int tn = 0, t1 = 0;
-            #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const uint32_t v = whist[ci * 256 + lane * 4 + k];
-                ln[k] = (int)(v & 0xFFFFu);
-                l1[k] = (int)(v >> 16);
-                tn += ln[k];
-                t1 += l1[k];
-            }
-            // both counts in one scan: n <= MID_N fits 16 bits each
-            const int sc = wave_scan_incl_i32(tn | (t1 << 16));
-            int cn = (sc & 0xFFFF) - tn, c1f = (sc >> 16) - t1;
-            double cand_s = -1.0;
-            int cand_b = -1, cand_nl = 0;
-            #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int b = lane * 4 + k;
-                cn += ln[k];
-                c1f += l1[k];
-                if (ln[k] == 0 || b < bmin || b >= bmax) continue;
-                const long nL = cn, n1L = c1f;
-                const long n0L = nL - n1L, nR = n - nL;
-                const long n1R = c1 - n1L, n0R = c0 - n0L;
-                const double s =
-                    (double)(n0L * n0L + n1L * n1L) / (double)nL
-                    + (double)(n0R * n0R + n1R * n1R) / (double)nR;
-                if (s > cand_s) { cand_s = s; cand_b = b; cand_nl = (int)nL; }
-            }
-            wave_argmax_mid(cand_s, cand_b, cand_nl);
-            // sequential select in perm order, strict > (phase-6 contract)
-            if (cand_b >= 0 && cand_s > best_s) {
-                best_s = cand_s;
-                bf = (int)((cand_pk >> (4 * ci)) & 15u);
-                bb = cand_b;
-                bnl = cand_nl;
-            }
+            double cand_s;
+            int cand_b, cand_nl;
+            wave_best_bin<true>(
+                [&](int b) { return unpack_counts(whist[ci * 256 + b]); },
+                (int)((cmin_pk >> (8 * ci)) & 0xFFu),
+                (int)((cmax_pk >> (8 * ci)) & 0xFFu), n, c0, c1,
+                cand_s, cand_b, cand_nl);
+            offer_split(best, cand_s, (int)((cand_pk >> (4 * ci)) & 15u),
+                        cand_b, cand_nl);
         }
     }
 
-    if (bf < 0) return;   // no valid split: leaf
-    const int nL = bnl;
+    if (best.feat < 0) return;   // no valid split: leaf
+    const int bf = best.feat, bb = best.bin, nL = best.nL;
 
     int lid = 0;
-    if (lane == 0) {
-        lid = atomicAdd(&a.node_alloc[it.job], 2);
-        a.nfeat[nbase + lid] = LEAF_SENTINEL;
-        a.nfeat[nbase + lid + 1] = LEAF_SENTINEL;
-        a.nfeat[nbase + node] = bf;
-        a.nsplit[nbase + node] = bb;
-        a.nleft[nbase + node] = lid;
-    }
+    if (lane == 0) lid = commit_split(a, it.job, nbase, node, bf, bb);
     lid = wave_bcast(lid, 0);
 
     // Stable partition of m_idx[ls, le) via this node's private m_idx2
@@ -1472,8 +1123,11 @@ __device__ __forceinline__ void mid_wave_node(
     }
 }
 
+// Waves per SIMD each variant is built for: the staged one is bounded by
+// its LDS (2 blocks per CU); the unstaged one fits 4 blocks per CU and must
+// stay within 128 VGPRs to use them.
 template <bool STAGED>
-__launch_bounds__(HBLK)
+__launch_bounds__(HBLK, STAGED ? 2 : 4)
 __global__ void mid_subtree_kernel(ForestDev a) {
     __shared__ uint4 m_codes[STAGED ? MID_N : 1];   // 32 KiB staged rows
     __shared__ int m_rows[MID_N];             // 8 KiB original global rows
@@ -1482,14 +1136,14 @@ __global__ void mid_subtree_kernel(ForestDev a) {
     __shared__ uint16_t m_idx[MID_N];
     __shared__ uint16_t m_idx2[MID_N];
     __shared__ uint32_t hist[FPAD * 256];     // 16 KiB packed histogram
-    __shared__ int sh_scan[HBLK];
+    __shared__ int sh_wsum[HBLK / 64];
     __shared__ int sh_bmin[FPAD], sh_bmax[FPAD];
     __shared__ int sh_cand[FPAD], sh_ncand;
     __shared__ double sh_score[FPAD];
     __shared__ int sh_bin[FPAD], sh_nL[FPAD];
-    __shared__ int sh_bestf, sh_bestbin, sh_bestnL, sh_lid;
+    __shared__ BestSplit sh_best;
+    __shared__ int sh_lid;
     __shared__ MidFrame stack[MID_STACK];
-    __shared__ int sh_lo, sh_ro;
     // this round's frames (one per wave in wave-parallel mode)
     __shared__ MidFrame wframes[HBLK / 64];
     __shared__ int sh_count, sh_take, sh_nblock;
@@ -1532,7 +1186,6 @@ __global__ void mid_subtree_kernel(ForestDev a) {
         // the smaller one on top.
         auto block_node = [&](int ls, int le, int depth, int node) {
             const int n = le - ls;
-            const int max_features = a.j_mf[it.job];
             const int splitter_random = a.j_rand[it.job];
             // global job-relative range (the RNG identity)
             const int gs = it.start + ls;
@@ -1557,15 +1210,9 @@ __global__ void mid_subtree_kernel(ForestDev a) {
             }
             __syncthreads();
 
-            // class counts (wave reduce over feature-0 histogram)
-            {
-                const int v = wave_sum_i32((int)(hist[tid] >> 16));
-                if (lane == 0) sh_scan[wave] = v;
-            }
-            __syncthreads();
-            const int c1 = sh_scan[0] + sh_scan[1] + sh_scan[2] + sh_scan[3];
+            // class counts from the feature-0 histogram
+            const int c1 = block_sum_i32((int)(hist[tid] >> 16), sh_wsum);
             const int c0 = n - c1;
-            __syncthreads();
 
             if (tid == 0) {
                 a.ncnt0[nbase + node] = (float)c0;
@@ -1576,123 +1223,48 @@ __global__ void mid_subtree_kernel(ForestDev a) {
                 return;
             }
 
-            // occupied-bin range per feature
-            if (tid < F) {
-                sh_bmin[tid] = 256;
-                sh_bmax[tid] = -1;
-            }
-            __syncthreads();
-            {
-                const int f3 = tid >> 4;
-                const int seg = (tid & 15) * 16;
-                if (f3 < F) {
-                    int lo = 256, hi = -1;
-                    for (int b = seg; b < seg + 16; ++b)
-                        if (hist[f3 * 256 + b] & 0xFFFFu) {
-                            if (lo == 256) lo = b;
-                            hi = b;
-                        }
-                    if (hi >= 0) {
-                        atomicMin(&sh_bmin[f3], lo);
-                        atomicMax(&sh_bmax[f3], hi);
-                    }
-                }
-            }
-            __syncthreads();
+            block_bin_ranges(
+                F, [&](int f, int b) { return hist[f * 256 + b] & 0xFFFFu; },
+                sh_bmin, sh_bmax);
 
-            // permutation (wave 0, in a register) + candidate walk
-            if (wave == 0) {
-                const uint64_t perm = feature_perm(
-                    philox_draw(TAG_FEATSEL | ((uint32_t)(depth & 0xFF) << 8),
-                                (uint32_t)gs, (uint32_t)ge,
-                                (uint32_t)(lane < FPAD ? lane : 0),
-                                a.seed, key),
-                    F);
-                if (lane == 0) {
-                    int nc = 0;
-                    for (int i = 0; i < F && nc < max_features; ++i) {
-                        const int f = perm_at(perm, i);
-                        if (sh_bmin[f] != sh_bmax[f]) sh_cand[nc++] = f;
-                    }
-                    sh_ncand = nc;
-                }
-            }
-            __syncthreads();
-
-            const int ncand = sh_ncand;
+            // permutation + candidate walk; ET: sh_bin[ci] takes candidate
+            // ci's drawn bin, which is the bin its evaluation reports
+            const int ncand = block_candidates(
+                a, key, depth, gs, ge, a.j_mf[it.job], splitter_random,
+                sh_bmin, sh_bmax, sh_cand, sh_bin, &sh_ncand);
             if (ncand == 0) {
                 __syncthreads();
                 return;
             }
 
-            // evaluate candidates (wave per candidate; identical math and
-            // tie-breaks to hist_split_kernel phase 5)
+            // evaluate candidates, one wave per candidate
             for (int ci = wave; ci < ncand; ci += HBLK / 64) {
                 const int f = sh_cand[ci];
-                const int bmin = sh_bmin[f], bmax = sh_bmax[f];
-                int ln[4], l1[4];
-                int tn = 0, t1 = 0;
-                for (int k = 0; k < 4; ++k) {
-                    uint32_t v = hist[f * 256 + lane * 4 + k];
-                    ln[k] = (int)(v & 0xFFFFu);
-                    l1[k] = (int)(v >> 16);
-                    tn += ln[k];
-                    t1 += l1[k];
-                }
-                // both counts in one scan: n <= MID_N fits 16 bits each
-                const int scp = wave_scan_incl_i32(tn | (t1 << 16));
-                const int excl_n = (scp & 0xFFFF) - tn;
-                const int excl_1 = (scp >> 16) - t1;
-
-                double best_s = -1.0;
-                int best_b = -1, best_nl = 0;
-
+                double best_s;
+                int best_b, best_nl;
                 if (splitter_random) {
-                    uint32_t tag = TAG_THRESH |
-                                   ((uint32_t)(depth & 0xFF) << 8);
-                    uint32_t u = philox_draw(tag, (uint32_t)gs,
-                                             (uint32_t)ge, (uint32_t)f,
-                                             a.seed, key);
-                    int b = bmin + (int)philox_bounded(
-                        u, (uint32_t)(bmax - bmin));
-                    if (b >= lane * 4 && b < lane * 4 + 4) {
-                        int cn = excl_n, c1f = excl_1;
-                        #pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            if (k > b - lane * 4) break;
-                            cn += ln[k];
-                            c1f += l1[k];
-                        }
-                        long nL = cn, n1L = c1f;
-                        long n0L = nL - n1L, nR = n - nL;
-                        long n1R = c1 - n1L, n0R = c0 - n0L;
-                        best_s = (double)(n0L * n0L + n1L * n1L)
-                                     / (double)nL
-                               + (double)(n0R * n0R + n1R * n1R)
-                                     / (double)nR;
-                        best_b = b;
-                        best_nl = (int)nL;
-                    }
-                } else {
-                    int cn = excl_n, c1f = excl_1;
+                    // ET: left counts at the drawn bin = the row's counts
+                    // over bins <= it (both in one sum: n <= MID_N).  The
+                    // bin lies in [bmin, bmax), so neither child is empty.
+                    best_b = sh_bin[ci];
+                    int part = 0;
+                    #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        int b = lane * 4 + k;
-                        cn += ln[k];
-                        c1f += l1[k];
-                        if (ln[k] == 0 || b < bmin || b >= bmax) continue;
-                        long nL = cn, n1L = c1f;
-                        long n0L = nL - n1L, nR = n - nL;
-                        long n1R = c1 - n1L, n0R = c0 - n0L;
-                        double sc2 = (double)(n0L * n0L + n1L * n1L)
-                                         / (double)nL
-                                   + (double)(n0R * n0R + n1R * n1R)
-                                         / (double)nR;
-                        if (sc2 > best_s) {
-                            best_s = sc2; best_b = b; best_nl = (int)nL;
-                        }
+                        const int b = lane * 4 + k;
+                        part += b <= best_b ? (int)hist[f * 256 + b] : 0;
                     }
+                    const uint2 t =
+                        unpack_counts((uint32_t)wave_sum_i32(part));
+                    best_nl = (int)t.x;
+                    best_s = split_score(t.x, t.y, n, c0, c1);
+                } else {
+                    wave_best_bin<true>(
+                        [&](int b) {
+                            return unpack_counts(hist[f * 256 + b]);
+                        },
+                        sh_bmin[f], sh_bmax[f], n, c0, c1, best_s, best_b,
+                        best_nl);
                 }
-                wave_argmax_mid(best_s, best_b, best_nl);
                 if (lane == 0) {
                     sh_score[ci] = best_s;
                     sh_bin[ci] = best_b;
@@ -1701,77 +1273,36 @@ __global__ void mid_subtree_kernel(ForestDev a) {
             }
             __syncthreads();
 
+            // select in permutation order and commit (thread 0)
             if (tid == 0) {
-                double best_s = -1.0e300;
-                int bf = -1, bb = -1, bnl = 0;
-                for (int ci = 0; ci < ncand; ++ci) {
-                    if (sh_bin[ci] >= 0 && sh_score[ci] > best_s) {
-                        best_s = sh_score[ci];
-                        bf = sh_cand[ci];
-                        bb = sh_bin[ci];
-                        bnl = sh_nL[ci];
-                    }
-                }
-                sh_bestf = bf;
-                sh_bestbin = bb;
-                sh_bestnL = bnl;
-                if (bf >= 0) {
-                    int l = atomicAdd(&a.node_alloc[it.job], 2);
-                    a.nfeat[nbase + l] = LEAF_SENTINEL;
-                    a.nfeat[nbase + l + 1] = LEAF_SENTINEL;
-                    a.nfeat[nbase + node] = bf;
-                    a.nsplit[nbase + node] = bb;
-                    a.nleft[nbase + node] = l;
-                    sh_lid = l;
-                }
+                BestSplit best = no_split();
+                for (int ci = 0; ci < ncand; ++ci)
+                    offer_split(best, sh_score[ci], sh_cand[ci], sh_bin[ci],
+                                sh_nL[ci]);
+                sh_best = best;
+                if (best.feat >= 0)
+                    sh_lid = commit_split(a, it.job, nbase, node, best.feat,
+                                          best.bin);
             }
             __syncthreads();
 
-            const int bf = sh_bestf;
-            if (bf < 0) {
+            const BestSplit best = sh_best;
+            if (best.feat < 0) {
                 __syncthreads();
                 return;
             }
-            const int bb = sh_bestbin;
-            const int nL = sh_bestnL;
+            const int nL = best.nL;
 
-            // stable partition of m_idx[ls,le) via m_idx2 (LDS)
-            if (tid == 0) { sh_lo = 0; sh_ro = 0; }
-            __syncthreads();
-            for (int base = ls; base < le; base += HBLK) {
-                const int i = base + tid;
-                const bool valid = i < le;
-                int o = 0, flag = 0;
-                if (valid) {
-                    o = m_idx[i];   // whole entry: the label bit moves too
-                    const uint4 cw = code_at(o & MID_IDX_MASK);
-                    flag = (int)(code_byte(cw, bf) <= (uint32_t)bb);
-                }
-                const unsigned long long lm = __ballot(valid && flag);
-                const unsigned long long below = (1ULL << lane) - 1ULL;
-                const int left_rank = __popcll(lm & below);
-                if (lane == 0) sh_scan[wave] = __popcll(lm);
-                __syncthreads();
-                int wave_left_excl = 0;
-                for (int ww = 0; ww < wave; ++ww)
-                    wave_left_excl += sh_scan[ww];
-                const int tile_left = sh_scan[0] + sh_scan[1] + sh_scan[2]
-                                      + sh_scan[3];
-                const int tile_n = min(HBLK, le - base);
-                if (valid) {
-                    const int dst = flag
-                        ? ls + sh_lo + wave_left_excl + left_rank
-                        : ls + nL + sh_ro + (i - base)
-                          - (wave_left_excl + left_rank);
-                    m_idx2[dst] = (uint16_t)o;
-                }
-                __syncthreads();
-                if (tid == 0) {
-                    sh_lo += tile_left;
-                    sh_ro += tile_n - tile_left;
-                }
-                __syncthreads();
-            }
+            // stable partition of m_idx[ls,le) via m_idx2 (LDS); the whole
+            // entry moves, its label bit with it
+            block_partition(
+                ls, le, nL, sh_wsum,
+                [&](int i, int& o) {
+                    o = m_idx[i];
+                    return code_byte(code_at(o & MID_IDX_MASK), best.feat)
+                           <= (uint32_t)best.bin;
+                },
+                [&](int dst, int o) { m_idx2[dst] = (uint16_t)o; });
             for (int i = ls + tid; i < le; i += HBLK) m_idx[i] = m_idx2[i];
             __syncthreads();
 
@@ -1933,26 +1464,12 @@ __global__ void small_subtree_kernel(ForestDev a) {
             }
             if (n < 2 || c0 == 0 || c1 == 0) continue;
 
-            // feature permutation: each of the first F-1 lanes computes
-            // its Philox draw and swap target in parallel; the swaps run
-            // wave-uniformly in a 64-bit register (wave_ops.h)
-            const uint64_t perm = feature_perm(
-                philox_draw(TAG_FEATSEL | ((uint32_t)(depth & 0xFF) << 8),
-                            (uint32_t)s, (uint32_t)e,
-                            (uint32_t)(lane < FPAD ? lane : 0), a.seed, key),
-                F);
+            // feature permutation in a 64-bit register (wave_ops.h)
+            const uint64_t perm = featsel_perm(a, key, depth, s, e);
+            const uint32_t u_thresh =
+                splitter_random ? thresh_draws(a, key, depth, s, e) : 0u;
 
-            uint32_t u_thresh = 0;
-            if (splitter_random) {
-                uint32_t ttag = TAG_THRESH |
-                                ((uint32_t)(depth & 0xFF) << 8);
-                u_thresh = philox_draw(ttag, (uint32_t)s, (uint32_t)e,
-                                       (uint32_t)(lane < FPAD ? lane : 0),
-                                       a.seed, key);
-            }
-
-            double best_s = -1.0e300;
-            int best_f = -1, best_b = -1, best_nl = 0;
+            BestSplit best = no_split();
             int n_eval = 0;
 
             for (int pi = 0; pi < F && n_eval < max_features; ++pi) {
@@ -1972,24 +1489,15 @@ __global__ void small_subtree_kernel(ForestDev a) {
                 ++n_eval;
 
                 if (splitter_random) {
-                    const int b = cmin + (int)philox_bounded(
-                        wave_bcast(u_thresh, f), (uint32_t)(cmax - cmin));
+                    const int b = et_bin(u_thresh, f, cmin, cmax);
                     const unsigned long long lm =
                         mask & __ballot(in && my_code <= b);
-                    const long nL = __popcll(lm);
-                    const long n1L = __popcll(lm & lab_mask);
-                    const long n0L = nL - n1L, nR = n - nL;
-                    const long n1R = c1 - n1L, n0R = c0 - n0L;
-                    if (nL > 0 && nR > 0) {
-                        double sc = (double)(n0L * n0L + n1L * n1L)
-                                        / (double)nL
-                                    + (double)(n0R * n0R + n1R * n1R)
-                                        / (double)nR;
-                        if (sc > best_s) {
-                            best_s = sc; best_f = f; best_b = b;
-                            best_nl = (int)nL;
-                        }
-                    }
+                    const int nL = __popcll(lm);
+                    if (nL > 0 && nL < n)
+                        offer_split(best,
+                                    split_score(nL, __popcll(lm & lab_mask),
+                                                n, c0, c1),
+                                    f, b, nL);
                 } else {
                     // parallel-rank: every in-mask lane scores its OWN
                     // code as the threshold candidate (duplicates give
@@ -2017,40 +1525,27 @@ __global__ void small_subtree_kernel(ForestDev a) {
                     double sc = -1.0e300;
                     int sb = 0x7FFFFFFF, snl = 0;
                     if (in && my_code < cmax) {
-                        const long nL = cnt, n1L = cnt1;
-                        const long n0L = nL - n1L, nR = n - nL;
-                        const long n1R = c1 - n1L, n0R = c0 - n0L;
-                        sc = (double)(n0L * n0L + n1L * n1L) / (double)nL
-                           + (double)(n0R * n0R + n1R * n1R) / (double)nR;
+                        sc = split_score(cnt, cnt1, n, c0, c1);
                         sb = my_code;
-                        snl = (int)nL;
+                        snl = cnt;
                     }
                     wave_argmax_small(sc, sb, snl);
-                    if (sc > best_s) {
-                        best_s = sc; best_f = f; best_b = sb;
-                        best_nl = snl;
-                    }
+                    offer_split(best, sc, f, sb, snl);
                 }
             }
 
-            if (best_f < 0) continue;   // no valid split: leaf
+            if (best.feat < 0) continue;   // no valid split: leaf
+            const int best_f = best.feat, best_b = best.bin, nL = best.nL;
 
             int lid = 0;
-            if (lane == 0) {
-                lid = atomicAdd(&a.node_alloc[it.job], 2);
-                a.nfeat[nbase + lid] = LEAF_SENTINEL;
-                a.nfeat[nbase + lid + 1] = LEAF_SENTINEL;
-                a.nfeat[nbase + node] = best_f;
-                a.nsplit[nbase + node] = best_b;
-                a.nleft[nbase + node] = lid;
-            }
+            if (lane == 0)
+                lid = commit_split(a, it.job, nbase, node, best_f, best_b);
             lid = wave_bcast(lid, 0);
 
             const int bc = (int)((w[best_f >> 2] >> ((best_f & 3) * 8))
                                  & 0xFFu);
             const unsigned long long lmask =
                 mask & __ballot(((mask >> lane) & 1ULL) && bc <= best_b);
-            const int nL = best_nl;
 
             if (lane == 0) {
                 stack[sp + 1] = {mask & ~lmask, s + nL, e, depth + 1,
@@ -2134,55 +1629,6 @@ __global__ void predict_combine_kernel(
     const int pred = acc1 > acc0;
     pred_out[p] = (uint8_t)pred;
     const int row = pair_row[p];
-    const int k = 2 * (int)y_test[row] + pred - 1;
-    if (k >= 0) {
-        atomicAdd(&confusion[proj_id[row] * 3 + k], 1);
-        atomicAdd(&confusion[n_proj * 3 + k], 1);
-    }
-}
-
-// (single-stage original, no longer launched — kept for reference builds)
-__global__ void predict_confusion_kernel(
-    const uint8_t* __restrict__ codes_test,   // [M, FPAD] full-dataset codes
-    const uint8_t* __restrict__ y_test,       // [M]
-    const int* __restrict__ proj_id,          // [M] project index per row
-    const int* __restrict__ pair_row,         // [P] dataset row of pair
-    const int* __restrict__ pair_fold,        // [P] fold of pair
-    int n_pairs,
-    const long* __restrict__ j_node_off,      // [J]
-    const int* __restrict__ nfeat, const int* __restrict__ nsplit,
-    const int* __restrict__ nleft,
-    const float* __restrict__ ncnt0, const float* __restrict__ ncnt1,
-    int trees_per_fold,
-    uint8_t* __restrict__ pred_out,           // [P]
-    int* __restrict__ confusion,              // [n_proj+1, 3]
-    int n_proj) {
-    int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n_pairs) return;
-
-    const int row = pair_row[p];
-    const int fold = pair_fold[p];
-    const uint8_t* cr = codes_test + (size_t)row * FPAD;
-
-    double acc0 = 0.0, acc1 = 0.0;
-    for (int t = 0; t < trees_per_fold; ++t) {
-        const long nbase = j_node_off[fold * trees_per_fold + t];
-        int node = 0;
-        int f = nfeat[nbase];
-        while (f != LEAF_SENTINEL) {
-            int go_right = (int)cr[f] > nsplit[nbase + node];
-            node = nleft[nbase + node] + go_right;
-            f = nfeat[nbase + node];
-        }
-        double c0 = (double)ncnt0[nbase + node];
-        double c1 = (double)ncnt1[nbase + node];
-        double tot = c0 + c1;
-        acc0 += c0 / tot;
-        acc1 += c1 / tot;
-    }
-    const int pred = acc1 > acc0;
-    pred_out[p] = (uint8_t)pred;
-
     const int k = 2 * (int)y_test[row] + pred - 1;
     if (k >= 0) {
         atomicAdd(&confusion[proj_id[row] * 3 + k], 1);

@@ -19,75 +19,15 @@
 #define KNN_BLK 256
 #define HWAVES (KNN_BLK / 64)
 
-// knn_kernel: for each query row, the k nearest candidate rows.
-// X: [n, FPAD] fp32 (padded features are zero).  skip_identity: candidate
-// j == query j excluded (query set IS candidate set).
-__launch_bounds__(KNN_BLK)
-__global__ void knn_kernel(const float* __restrict__ X,
-                           int n, int k, int skip_identity,
-                           int* __restrict__ out /* [n, k] */) {
-    __shared__ float tile[KNN_BLK][FPAD];
-
-    const int q = blockIdx.x * KNN_BLK + threadIdx.x;
-
-    float qv[FPAD];
-    if (q < n) {
-        #pragma unroll
-        for (int f = 0; f < FPAD; ++f) qv[f] = X[(size_t)q * FPAD + f];
-    }
-
-    double bd[KMAX];
-    int bi[KMAX];
-    for (int j = 0; j < KMAX; ++j) { bd[j] = 1.0e300; bi[j] = -1; }
-
-    for (int base = 0; base < n; base += KNN_BLK) {
-        const int c = base + threadIdx.x;
-        if (c < n) {
-            #pragma unroll
-            for (int f = 0; f < FPAD; ++f)
-                tile[threadIdx.x][f] = X[(size_t)c * FPAD + f];
-        }
-        __syncthreads();
-
-        if (q < n) {
-            const int tn = min(KNN_BLK, n - base);
-            for (int t = 0; t < tn; ++t) {
-                const int cand = base + t;
-                if (skip_identity && cand == q) continue;
-                double d = 0.0;
-                #pragma unroll
-                for (int f = 0; f < FPAD; ++f) {
-                    double diff = (double)qv[f] - (double)tile[t][f];
-                    d = d + diff * diff;
-                }
-                // insertion into the sorted top-k (ties: lower index first,
-                // i.e. strictly-less replaces — candidates arrive in
-                // ascending index order)
-                if (d < bd[k - 1]) {
-                    int j = k - 1;
-                    while (j > 0 && d < bd[j - 1]) {
-                        bd[j] = bd[j - 1];
-                        bi[j] = bi[j - 1];
-                        --j;
-                    }
-                    bd[j] = d;
-                    bi[j] = cand;
-                }
-            }
-        }
-        __syncthreads();
-    }
-
-    if (q < n)
-        for (int j = 0; j < k; ++j) out[(size_t)q * k + j] = bi[j];
-}
-
-// Segmented (fold-batched) k-NN: one call covers many independent
+// Segmented (fold-batched) k-NN: for each query row, the k nearest
+// candidate rows of its own segment.  One call covers many independent
 // candidate sets (e.g. the 10 CV folds of a balance group) so the chip is
-// filled even when each segment alone is small.  seg_off[Nseg+1] bounds the
-// segments in X; seg_blk[Nseg+1] is the prefix of per-segment block counts
-// (ceil(n_seg / KNN_BLK)); outputs are SEGMENT-LOCAL indices — identical
-// bits to a per-segment knn_kernel call.
+// filled even when each segment alone is small.  X: [n, FPAD] fp32 (padded
+// features are zero); seg_off[Nseg+1] bounds the segments in X; seg_blk
+// [Nseg+1] is the prefix of per-segment block counts (ceil(n_seg /
+// KNN_BLK)).  skip_identity: candidate j == query j excluded (the query
+// set IS the candidate set).  Outputs are SEGMENT-LOCAL indices, so a
+// segment's result does not depend on what else is in the batch.
 __launch_bounds__(KNN_BLK)
 __global__ void knn_segmented_kernel(const float* __restrict__ X,
                                      const int* __restrict__ seg_off,

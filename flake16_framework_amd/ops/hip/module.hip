@@ -244,8 +244,6 @@ static std::vector<at::Tensor> forest_fit_impl(
     if (const char* e = getenv("FLAKE16_DRAIN_AT"))
         small_drain_at = mid_drain_at = atol(e);
     const bool drain_stats = getenv("FLAKE16_DRAIN_STATS") != nullptr;
-    // ablation switch for the level kernels (see level_ops)
-    const bool rf_candonly = getenv("FLAKE16_RF_CANDONLY") != nullptr;
     long n_drains = 0;
 
     auto launch_mid = [&](int grid) {
@@ -304,15 +302,9 @@ static std::vector<at::Tensor> forest_fit_impl(
         a.cur_count = st + cur_par * 4;
         a.nxt_count = st + nx * 4;
         if (any_best) {
-            if (!has_wide && rf_candonly) {
-                // ablation variant: candidate-only RF histograms measured
-                // ~3% SLOWER than full histograms + subtraction pools
-                rf_cand_split_kernel<<<lv_grid, HBLK, 0, stream>>>(a);
-            } else {
-                hist_split_kernel<false><<<lv_grid, HBLK, 0, stream>>>(a);
-                if (has_wide)
-                    hist_split_kernel<true><<<lv_grid, HBLK, 0, stream>>>(a);
-            }
+            hist_split_kernel<false><<<lv_grid, HBLK, 0, stream>>>(a);
+            if (has_wide)
+                hist_split_kernel<true><<<lv_grid, HBLK, 0, stream>>>(a);
         }
         if (any_rand)
             et_split_kernel<<<lv_grid, HBLK, 0, stream>>>(a);

@@ -212,10 +212,3 @@ __global__ void pca_signflip_kernel(double* __restrict__ T, int n, int F) {
     for (int i = threadIdx.x; i < n; i += RBLK)
         T[(size_t)i * FPAD + k] *= sgn;
 }
-
-// fp64 -> fp32 matrix cast (the engine bins fp32 values).
-__global__ void cast_f64_f32_kernel(const double* __restrict__ in,
-                                    float* __restrict__ out, long count) {
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count) out[i] = (float)in[i];
-}

@@ -8,7 +8,7 @@
 //
 // EVERY primitive assumes a FULLY ACTIVE 64-lane wave (EXEC all ones):
 // DPP reads of inactive lanes are undefined.  All call sites are
-// wave-uniform code of the mid / small subtree kernels.
+// wave-uniform code of the forest kernels (forest.hip).
 //
 // Reduction shape (wave_reduce): row_shr:1,2,4,8 leave each 16-lane row's
 // reduction in its lane 15; row_bcast:15 folds row 0 into row 1 and row 2

@@ -6,6 +6,15 @@ subtree) keep the feature permutation in a register, reduce with DPP and
 carry the label in bit 15 of the staged sample index.  Every case fits
 trees with ops.forest_fit_multi and compares them node by node with
 models/forest_ref.py: the trees must be bit-identical.
+
+The test_band_* cases do the same for the level band (> 2048 samples):
+hist_split_kernel (RF, DT) and et_split_kernel (ET) build those nodes with
+the node steps they share with the subtree builders, one 256-thread block
+per node, partition the samples in 256-wide tiles and hand children of
+65..2048 samples a precomputed histogram from the subtraction pools.  The
+cases cover sizes either side of a partition-tile edge and with several
+band levels, F below the pad, constant columns, ties, degenerate labels,
+and the same trees with the pools switched off.
 """
 
 import numpy as np
@@ -172,9 +181,8 @@ def test_constant_deep_in_subtree(ops, dev):
     _check(ops, dev, codes, y, [64, 500, 2048])
 
 
-def _tie_codes(name):
+def _tie_codes(name, n=700):
     rng = np.random.RandomState(5)
-    n = 700
     if name == "duplicated_columns":
         # equal scores across candidates: strict > in permutation order
         return np.tile(rng.randint(0, 256, (n, 4)), (1, 4)).astype(np.uint8)
@@ -203,3 +211,82 @@ def test_labels(ops, dev, rand_data, labels):
     if labels == "one_positive":
         y[37] = 1   # inside every prefix below
     _check(ops, dev, codes, y, [64, 65, 2048])
+
+
+# ---------------------------------------------------------------------------
+# The level band: nodes above 2048 samples.
+# ---------------------------------------------------------------------------
+BAND_ROWS = 5000
+# 2304 = 9 x 256: 2304 and 2305 sit either side of a partition-tile edge;
+# 4096 and up give several band levels.
+BAND_SIZES = [2049, 2304, 2305, 4096, 4097, 5000]
+
+
+@pytest.fixture(scope="module")
+def band_data():
+    """Random 0..255 codes in all 16 columns, about 30 % positives."""
+    rng = np.random.RandomState(11)
+    codes = rng.randint(0, 256, (BAND_ROWS, 16)).astype(np.uint8)
+    y = (rng.rand(BAND_ROWS) < 0.3).astype(np.uint8)
+    return codes, y
+
+
+@pytest.fixture(scope="module")
+def band_refs(band_data):
+    """Reference trees of the band-size batch, computed once."""
+    codes, y = band_data
+    return _reference(codes, y, BAND_SIZES, 16)
+
+
+def test_band_sizes(ops, dev, band_data, band_refs):
+    codes, y = band_data
+    _check(ops, dev, codes, y, BAND_SIZES, refs=band_refs)
+
+
+def test_band_sizes_without_pools(ops, dev, band_data, band_refs,
+                                  monkeypatch):
+    """No node gets a histogram slot: 65..2048 children go to the mid
+    kernel instead of coming back through hist_split_kernel with one."""
+    monkeypatch.setenv("FLAKE16_HIST_SAVE_MIN", "1000000")
+    codes, y = band_data
+    _check(ops, dev, codes, y, BAND_SIZES, refs=band_refs)
+
+
+@pytest.mark.parametrize("F", [1, 2, 7, 16])
+def test_band_f_below_pad(ops, dev, band_data, F):
+    """Columns >= F hold random data: a read past F changes a tree."""
+    codes, y = band_data
+    _check(ops, dev, codes, y, [4097], F=F)
+
+
+@pytest.mark.parametrize("n_const", [12, 14, 15, 16])
+def test_band_constant_columns(ops, dev, band_data, n_const):
+    """As test_constant_columns; 16 leaves the root a single leaf, the
+    no-candidate exit of both level kernels."""
+    codes, y = band_data
+    codes = codes.copy()
+    rng = np.random.RandomState(n_const)
+    const_cols = rng.permutation(16)[:n_const]
+    codes[:, const_cols] = (const_cols + 3).astype(np.uint8)
+    _check(ops, dev, codes, y, [BAND_ROWS])
+
+
+@pytest.mark.parametrize("name", ["duplicated_columns", "binary",
+                                  "byte_range_ends", "across_bit_7"])
+def test_band_ties(ops, dev, name):
+    """Strict > across duplicated columns and the lowest-bin rule in the
+    level kernels."""
+    codes = _tie_codes(name, BAND_ROWS)
+    y = (np.random.RandomState(6).rand(BAND_ROWS) < 0.3).astype(np.uint8)
+    _check(ops, dev, codes, y, [BAND_ROWS])
+
+
+@pytest.mark.parametrize("labels", ["all_zero", "all_one", "one_positive"])
+def test_band_labels(ops, dev, band_data, labels):
+    """The leaf exit before the candidate walk (single-node trees for the
+    first two)."""
+    codes, _ = band_data
+    y = np.full(BAND_ROWS, labels == "all_one", dtype=np.uint8)
+    if labels == "one_positive":
+        y[37] = 1
+    _check(ops, dev, codes, y, [BAND_ROWS])
