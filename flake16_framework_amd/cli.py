@@ -30,6 +30,16 @@ GPU/synthetic extensions:
                              {"feature_names", "base_value", "tests":
                              {proj: {nodeid: [proba, pred, phi...]}}};
                              class-1 values, the negation of shap.pkl's
+  holdout [--config nod|od] [--keys K0 K1 K2 K3 K4] [--backend B]
+      [--tests-file F] [--out F] [--n-trees N] [--thresholds K]
+      [--detections F]
+                             leave-one-project-out evaluation: every
+                             project is classified by a detector fitted on
+                             the other projects only -> holdout.json with
+                             per-project and pooled [FP, FN, TP] under the
+                             argmax rule and under proba >= k / (K - 1);
+                             --detections also writes the out-of-fold
+                             {proj: {nodeid: [proba, pred]}}
 
 Distributed: launch via `python -m torch.distributed.run --nproc-per-node N
 experiment.py scores` — one rank per GPU over RCCL; rank 0 writes the
@@ -140,6 +150,38 @@ def main(argv=None):
                         for f in np.argsort(-weight, kind="stable")[:3])
         print(f"wrote {out} ({len(res['pred'])} tests; "
               f"largest mean |phi|: {top})")
+    elif command == "holdout":
+        from .configgrid import SHAP_CONFIGS
+        from .constants import HOLDOUT_FILE, TESTS_FILE
+        from .engine.holdout import best_f1_threshold, write_holdout
+        config = _pop_flag(args, "--config", "nod")
+        if config not in ("nod", "od"):
+            raise ValueError("--config takes nod or od")
+        keys = SHAP_CONFIGS[("nod", "od").index(config)]
+        if "--keys" in args:
+            i = args.index("--keys")
+            keys = tuple(args[i + 1:i + 6])
+            if len(keys) != 5:
+                raise ValueError("--keys takes five config keys")
+            del args[i:i + 6]
+        backend = _pop_flag(args, "--backend", "auto")
+        tests_file = _pop_flag(args, "--tests-file", TESTS_FILE)
+        out = _pop_flag(args, "--out", HOLDOUT_FILE)
+        n_trees = _pop_flag(args, "--n-trees", None)
+        n_thresholds = int(_pop_flag(args, "--thresholds", "101"))
+        detections = _pop_flag(args, "--detections", None)
+        res = write_holdout(keys, tests_file=tests_file, out_file=out,
+                            detections_file=detections, backend=backend,
+                            n_trees=int(n_trees) if n_trees else None,
+                            n_thresholds=n_thresholds)
+        fmt = lambda v: "n/a" if v is None else f"{v:.4f}"
+        p, r, f = res["total"]["argmax"][3:]
+        best = best_f1_threshold(res["total"]["curve"], res["thresholds"])
+        best = ("none" if best is None
+                else f"{best[1]:.4f} (F1 {best[2]:.4f}, descriptive)")
+        print(f"wrote {out} ({len(res['projects'])} held-out projects, "
+              f"{res['n_trees']} trees; pooled argmax P {fmt(p)} "
+              f"R {fmt(r)} F1 {fmt(f)}; best-F1 threshold {best})")
     elif command == "figures":
         offline = _pop_flag(args, "--offline", False, boolean=True)
         from .report.figures import write_figures

@@ -18,6 +18,7 @@ SCORES_FILE = "scores.pkl"
 DETECTOR_FILE = "detector.npz"
 DETECTIONS_FILE = "detections.json"
 EXPLANATIONS_FILE = "explanations.json"
+HOLDOUT_FILE = "holdout.json"
 SUBJECTS_FILE = "subjects.txt"
 REQUIREMENTS_FILE = "requirements.txt"
 

@@ -15,9 +15,11 @@
 #include "treeshap.hip"
 #include "detect.hip"
 #include "explain.hip"
+#include "holdout.hip"
 
 #include <vector>
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 
@@ -835,6 +837,185 @@ at::Tensor detector_shap(at::Tensor codes, at::Tensor tree_leaf_off,
     return phi;
 }
 
+// ---------------------------------------------------------------------------
+// grouped leave-one-project-out evaluation (holdout.hip)
+// ---------------------------------------------------------------------------
+// seg_off arrives CPU-resident (int32 [G + 1]): the block table is built
+// from its values, and nothing on the device indexes with an unchecked
+// offset.  Returns the int4 (group, first row, end row, 0) table for
+// `rows` rows per block on `dev`; groups without rows get no block.
+static at::Tensor holdout_block_table(const at::Tensor& seg_off, long M,
+                                      int rows, c10::Device dev,
+                                      const char* op) {
+    TORCH_CHECK(!seg_off.is_cuda() && seg_off.dtype() == at::kInt &&
+                seg_off.dim() == 1 && seg_off.is_contiguous() &&
+                seg_off.numel() >= 2, op, ": seg_off must be CPU int32 [G+1]");
+    TORCH_CHECK(M < (1L << 31));
+    const int G = (int)seg_off.numel() - 1;
+    const int* so = seg_off.data_ptr<int>();
+    TORCH_CHECK(so[0] == 0 && so[G] == M, op,
+                ": seg_off must run from 0 to the row count");
+    std::vector<int> tab;
+    for (int g = 0; g < G; ++g) {
+        TORCH_CHECK(so[g + 1] >= so[g], op, ": seg_off steps back at group ",
+                    g);
+        for (int r = so[g]; r < so[g + 1]; r += rows) {
+            tab.push_back(g);
+            tab.push_back(r);
+            tab.push_back(so[g + 1]);
+            tab.push_back(0);
+        }
+    }
+    auto t = at::empty({(long)tab.size() / 4, 4}, at::kInt);
+    std::copy(tab.begin(), tab.end(), t.data_ptr<int>());
+    return t.to(dev);
+}
+
+// detect_encode per group: rows seg_off[g]:seg_off[g+1] are encoded with
+// row g of mean / scale / pca_mean / W and with group g's cuts.  cut_off
+// row g holds group-local offsets (a detector's own cut_off); the groups'
+// cuts lie back to back in `cuts`.
+at::Tensor holdout_encode(at::Tensor X, at::Tensor seg_off, at::Tensor mean,
+                          at::Tensor scale, at::Tensor pca_mean,
+                          at::Tensor W, bool has_pca, at::Tensor cuts,
+                          at::Tensor cut_off, int64_t F) {
+    TORCH_CHECK(X.is_cuda() && X.dtype() == at::kDouble && X.dim() == 2 &&
+                X.size(1) == FPAD && X.is_contiguous());
+    TORCH_CHECK(F >= 1 && F <= FPAD);
+    const long M = X.size(0);
+    auto dev = X.device();
+    auto tab = holdout_block_table(seg_off, M, DETECT_BLK, dev,
+                                   "holdout_encode");
+    const long G = seg_off.numel() - 1;
+    for (const at::Tensor* p : {&mean, &scale, &pca_mean, &W})
+        TORCH_CHECK(!p->is_cuda() && p->dtype() == at::kDouble &&
+                    p->is_contiguous());
+    TORCH_CHECK(mean.numel() == G * FPAD && scale.numel() == G * FPAD &&
+                pca_mean.numel() == G * FPAD &&
+                W.numel() == G * FPAD * FPAD,
+                "holdout_encode: one parameter set per group");
+    TORCH_CHECK(!cuts.is_cuda() && cuts.dtype() == at::kFloat &&
+                cuts.is_contiguous());
+    TORCH_CHECK(!cut_off.is_cuda() && cut_off.dtype() == at::kInt &&
+                cut_off.is_contiguous() &&
+                cut_off.numel() == G * (FPAD + 1));
+    const int* co = cut_off.data_ptr<int>();
+    auto cut_base = at::empty({G}, at::kInt);
+    long n_cuts = 0;
+    for (long g = 0; g < G; ++g, co += FPAD + 1) {
+        TORCH_CHECK(co[0] == 0, "holdout_encode: cut offsets of group ", g,
+                    " must start at 0");
+        for (int f = 0; f < FPAD; ++f)
+            TORCH_CHECK(co[f + 1] >= co[f] &&
+                        co[f + 1] - co[f] <= DETECT_MAX_CUTS,
+                        "holdout_encode: bad cut count for group ", g,
+                        " feature ", f);
+        cut_base.data_ptr<int>()[g] = (int)n_cuts;
+        n_cuts += co[FPAD];
+        TORCH_CHECK(n_cuts < (1L << 31));
+    }
+    TORCH_CHECK(n_cuts == cuts.numel(),
+                "holdout_encode: cut offsets do not cover the cut array");
+
+    const at::cuda::OptionalCUDAGuard guard(dev);
+    auto codes = at::empty({M, FPAD}, X.options().dtype(at::kByte));
+    if (M == 0) return codes;
+    auto mean_d = mean.to(dev), scale_d = scale.to(dev);
+    auto pmean_d = pca_mean.to(dev), W_d = W.to(dev);
+    auto cuts_d = cuts.to(dev), off_d = cut_off.to(dev);
+    auto base_d = cut_base.to(dev);
+    holdout_encode_kernel<<<(int)tab.size(0), DETECT_BLK, 0,
+                            current_stream()>>>(
+        X.data_ptr<double>(), (const int4*)tab.data_ptr<int>(),
+        mean_d.data_ptr<double>(), scale_d.data_ptr<double>(),
+        pmean_d.data_ptr<double>(), W_d.data_ptr<double>(), has_pca ? 1 : 0,
+        n_cuts ? cuts_d.data_ptr<float>() : nullptr, off_d.data_ptr<int>(),
+        base_d.data_ptr<int>(), (int)F, codes.data_ptr<uint8_t>());
+    return codes;
+}
+
+// forest_proba per group over one concatenated packed forest: group g
+// owns trees g * n_trees .. (g + 1) * n_trees - 1, node ids are global.
+// The caller guarantees well-formed forests, as for forest_proba.
+at::Tensor holdout_proba(at::Tensor codes, at::Tensor seg_off,
+                         at::Tensor tree_off, at::Tensor nodes_packed,
+                         int64_t n_trees) {
+    TORCH_CHECK(codes.is_cuda() && codes.dtype() == at::kByte &&
+                codes.dim() == 2 && codes.size(1) == FPAD &&
+                codes.is_contiguous());
+    const long M = codes.size(0);
+    auto tab = holdout_block_table(seg_off, M, HOLDOUT_PROBA_ROWS,
+                                   codes.device(), "holdout_proba");
+    const long G = seg_off.numel() - 1;
+    TORCH_CHECK(tree_off.is_cuda() && tree_off.dtype() == at::kLong &&
+                tree_off.is_contiguous() && n_trees >= 1 &&
+                n_trees < (1L << 20) &&
+                tree_off.numel() == G * n_trees + 1,
+                "holdout_proba: n_trees root ids per group and an end");
+    TORCH_CHECK(nodes_packed.is_cuda() && nodes_packed.dtype() == at::kInt &&
+                nodes_packed.dim() == 2 && nodes_packed.size(1) == 2 &&
+                nodes_packed.is_contiguous() &&
+                nodes_packed.size(0) < (1L << 31));
+    const at::cuda::OptionalCUDAGuard guard(codes.device());
+    const int n_blocks =
+        ((int)n_trees + PREDICT_TREE_BLOCK - 1) / PREDICT_TREE_BLOCK;
+    auto acc = at::empty({M, 2}, codes.options().dtype(at::kDouble));
+    if (M == 0) return acc;
+    holdout_proba_kernel<<<(int)tab.size(0), DETECT_BLK, 0,
+                           current_stream()>>>(
+        codes.data_ptr<uint8_t>(), (const int4*)tab.data_ptr<int>(),
+        tree_off.data_ptr<long>(), (const int2*)nodes_packed.data_ptr<int>(),
+        (int)n_trees, n_blocks, (double2*)acc.data_ptr<double>());
+    return acc;
+}
+
+// (curve int32 [G + 1, K, 3], argmax int32 [G + 1, 3]), columns FP, FN,
+// TP, row G pooled.  thresholds arrive CPU-resident and are checked here.
+std::vector<at::Tensor> threshold_counts(at::Tensor acc, at::Tensor labels,
+                                         at::Tensor seg_off, int64_t n_trees,
+                                         at::Tensor thresholds) {
+    TORCH_CHECK(acc.is_cuda() && acc.dtype() == at::kDouble &&
+                acc.dim() == 2 && acc.size(1) == 2 && acc.is_contiguous());
+    const long M = acc.size(0);
+    TORCH_CHECK(labels.is_cuda() && labels.dtype() == at::kByte &&
+                labels.dim() == 1 && labels.is_contiguous() &&
+                labels.numel() == M);
+    TORCH_CHECK(n_trees >= 1 && n_trees < (1L << 31));
+    TORCH_CHECK(!thresholds.is_cuda() && thresholds.dtype() == at::kDouble &&
+                thresholds.dim() == 1 && thresholds.is_contiguous());
+    const long K = thresholds.numel();
+    TORCH_CHECK(K >= 1 && K <= HOLDOUT_MAX_K,
+                "threshold_counts: between 1 and ", HOLDOUT_MAX_K,
+                " thresholds");
+    const double* th = thresholds.data_ptr<double>();
+    for (long k = 0; k < K; ++k)
+        TORCH_CHECK(std::isfinite(th[k]) && (k == 0 || th[k] > th[k - 1]),
+                    "threshold_counts: thresholds must be finite and "
+                    "strictly ascending");
+    auto tab = holdout_block_table(seg_off, M, DETECT_BLK, acc.device(),
+                                   "threshold_counts");
+    const long G = seg_off.numel() - 1;
+
+    const at::cuda::OptionalCUDAGuard guard(acc.device());
+    auto opts = acc.options().dtype(at::kInt);
+    // both outputs in one allocation, cleared by one memset
+    auto out = at::empty({(G + 1) * (K + 1) * 3}, opts);
+    hipStream_t s = current_stream();
+    TORCH_CHECK(hipMemsetAsync(out.data_ptr<int>(), 0,
+                               out.numel() * sizeof(int), s) == hipSuccess);
+    auto curve = out.narrow(0, 0, (G + 1) * K * 3).view({G + 1, K, 3});
+    auto argmax = out.narrow(0, (G + 1) * K * 3, (G + 1) * 3)
+                      .view({G + 1, 3});
+    if (M == 0) return {curve, argmax};
+    auto thr_d = thresholds.to(acc.device());
+    threshold_counts_kernel<<<(int)tab.size(0), DETECT_BLK, 0, s>>>(
+        (const double2*)acc.data_ptr<double>(), labels.data_ptr<uint8_t>(),
+        (const int4*)tab.data_ptr<int>(), thr_d.data_ptr<double>(), (int)K,
+        (int)n_trees, (int)G, curve.data_ptr<int>(),
+        argmax.data_ptr<int>());
+    return {curve, argmax};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("treeshap", &treeshap, py::call_guard<py::gil_scoped_release>(),
           "Path-dependent TreeSHAP (class-0), summed over trees");
@@ -880,4 +1061,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("detector_shap", &detector_shap,
           py::call_guard<py::gil_scoped_release>(),
           "Per-row class-1 TreeSHAP over a detector's merged leaf paths");
+    m.def("holdout_encode", &holdout_encode,
+          py::call_guard<py::gil_scoped_release>(),
+          "detect_encode with per-group parameters and cuts");
+    m.def("holdout_proba", &holdout_proba,
+          py::call_guard<py::gil_scoped_release>(),
+          "forest_proba with one forest per group, one launch");
+    m.def("threshold_counts", &threshold_counts,
+          py::call_guard<py::gil_scoped_release>(),
+          "Per-group [FP, FN, TP] under argmax and K probability thresholds");
 }
