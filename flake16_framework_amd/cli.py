@@ -40,6 +40,22 @@ GPU/synthetic extensions:
                              argmax rule and under proba >= k / (K - 1);
                              --detections also writes the out-of-fold
                              {proj: {nodeid: [proba, pred]}}
+  importance [--detector F] [--tests-file F] [--out F] [--repeats R]
+      [--seed S] [--threshold T] [--backend B]
+      [--holdout [--config nod|od | --keys K0 K1 K2 K3 K4] [--n-trees N]]
+                             permutation importance on a labelled
+                             tests.json: each raw feature, and each of the
+                             families Coverage / Resource Usage / Static,
+                             is permuted inside every project R times and
+                             the tests are classified again ->
+                             importance.json with the baseline and per
+                             group the pooled and per-project [FP, FN, TP]
+                             and the mean drop in F1 and recall.  The rule
+                             is argmax, or proba >= T with --threshold.
+                             --holdout fits one detector per held-out
+                             project first (as `holdout` does) and scores
+                             every project with the detector that never
+                             saw it
 
 Distributed: launch via `python -m torch.distributed.run --nproc-per-node N
 experiment.py scores` — one rank per GPU over RCCL; rank 0 writes the
@@ -182,6 +198,49 @@ def main(argv=None):
         print(f"wrote {out} ({len(res['projects'])} held-out projects, "
               f"{res['n_trees']} trees; pooled argmax P {fmt(p)} "
               f"R {fmt(r)} F1 {fmt(f)}; best-F1 threshold {best})")
+    elif command == "importance":
+        from .configgrid import SHAP_CONFIGS
+        from .constants import DETECTOR_FILE, IMPORTANCE_FILE, TESTS_FILE
+        from .engine.importance import holdout_importance, write_importance
+        leave_out = _pop_flag(args, "--holdout", False, boolean=True)
+        config = _pop_flag(args, "--config", "nod")
+        if config not in ("nod", "od"):
+            raise ValueError("--config takes nod or od")
+        keys = SHAP_CONFIGS[("nod", "od").index(config)]
+        if "--keys" in args:
+            i = args.index("--keys")
+            keys = tuple(args[i + 1:i + 6])
+            if len(keys) != 5:
+                raise ValueError("--keys takes five config keys")
+            del args[i:i + 6]
+        detector_file = _pop_flag(args, "--detector", DETECTOR_FILE)
+        tests_file = _pop_flag(args, "--tests-file", TESTS_FILE)
+        out = _pop_flag(args, "--out", IMPORTANCE_FILE)
+        n_trees = _pop_flag(args, "--n-trees", None)
+        threshold = _pop_flag(args, "--threshold", None)
+        kw = dict(repeats=int(_pop_flag(args, "--repeats", "5")),
+                  seed=int(_pop_flag(args, "--seed", "0")),
+                  threshold=None if threshold is None else float(threshold),
+                  backend=_pop_flag(args, "--backend", "auto"))
+        if leave_out:
+            res = holdout_importance(
+                keys, tests_file=tests_file, out_file=out,
+                n_trees=int(n_trees) if n_trees else None, **kw)
+        else:
+            from .engine.detector import Detector
+            res = write_importance(Detector.load(detector_file),
+                                   tests_file=tests_file, out_file=out, **kw)
+        fmt = lambda v: "n/a" if v is None else f"{v:.4f}"
+        drops = [(name, entry["f1_drop_mean"])
+                 for name, entry in res["importance"].items()]
+        # largest first, undefined last; ties keep the groups' order
+        drops.sort(key=lambda d: (d[1] is None, -(d[1] or 0.0)))
+        top = ", ".join(f"{name} {fmt(v)}" for name, v in drops[:3])
+        print(f"wrote {out} ({len(res['importance'])} groups x "
+              f"{res['repeats']} repeats, {res['rule']} rule"
+              f"{', leave-one-project-out' if leave_out else ''}; "
+              f"baseline F1 {fmt(res['baseline']['total'][5])}; "
+              f"largest mean F1 drop: {top})")
     elif command == "figures":
         offline = _pop_flag(args, "--offline", False, boolean=True)
         from .report.figures import write_figures

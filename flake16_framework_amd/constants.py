@@ -19,6 +19,7 @@ DETECTOR_FILE = "detector.npz"
 DETECTIONS_FILE = "detections.json"
 EXPLANATIONS_FILE = "explanations.json"
 HOLDOUT_FILE = "holdout.json"
+IMPORTANCE_FILE = "importance.json"
 SUBJECTS_FILE = "subjects.txt"
 REQUIREMENTS_FILE = "requirements.txt"
 

@@ -16,6 +16,7 @@
 #include "detect.hip"
 #include "explain.hip"
 #include "holdout.hip"
+#include "importance.hip"
 
 #include <vector>
 #include <algorithm>
@@ -843,10 +844,15 @@ at::Tensor detector_shap(at::Tensor codes, at::Tensor tree_leaf_off,
 // seg_off arrives CPU-resident (int32 [G + 1]): the block table is built
 // from its values, and nothing on the device indexes with an unchecked
 // offset.  Returns the int4 (group, first row, end row, 0) table for
-// `rows` rows per block on `dev`; groups without rows get no block.
+// `rows` rows per block on `dev`; groups without rows get no block.  With
+// det (int [G], checked by the caller) w holds the group's detector, and
+// with det_as_group x holds it as well, for the kernels that index their
+// parameters with x.
 static at::Tensor holdout_block_table(const at::Tensor& seg_off, long M,
                                       int rows, c10::Device dev,
-                                      const char* op) {
+                                      const char* op,
+                                      const int* det = nullptr,
+                                      bool det_as_group = false) {
     TORCH_CHECK(!seg_off.is_cuda() && seg_off.dtype() == at::kInt &&
                 seg_off.dim() == 1 && seg_off.is_contiguous() &&
                 seg_off.numel() >= 2, op, ": seg_off must be CPU int32 [G+1]");
@@ -860,15 +866,57 @@ static at::Tensor holdout_block_table(const at::Tensor& seg_off, long M,
         TORCH_CHECK(so[g + 1] >= so[g], op, ": seg_off steps back at group ",
                     g);
         for (int r = so[g]; r < so[g + 1]; r += rows) {
-            tab.push_back(g);
+            tab.push_back(det_as_group ? det[g] : g);
             tab.push_back(r);
             tab.push_back(so[g + 1]);
-            tab.push_back(0);
+            tab.push_back(det ? det[g] : 0);
         }
     }
     auto t = at::empty({(long)tab.size() / 4, 4}, at::kInt);
     std::copy(tab.begin(), tab.end(), t.data_ptr<int>());
     return t.to(dev);
+}
+
+// Host checks of G stacked parameter sets (CPU tensors): mean / scale /
+// pca_mean [G, FPAD], W [G, FPAD, FPAD], cut_off [G, FPAD + 1] with
+// group-local offsets into the groups' cuts, which lie back to back in
+// `cuts`.  Returns cut_base int32 [G] (CPU), each group's first cut.
+static at::Tensor grouped_params_check(const at::Tensor& mean,
+                                       const at::Tensor& scale,
+                                       const at::Tensor& pca_mean,
+                                       const at::Tensor& W,
+                                       const at::Tensor& cuts,
+                                       const at::Tensor& cut_off, long G,
+                                       const char* op) {
+    for (const at::Tensor* p : {&mean, &scale, &pca_mean, &W})
+        TORCH_CHECK(!p->is_cuda() && p->dtype() == at::kDouble &&
+                    p->is_contiguous());
+    TORCH_CHECK(mean.numel() == G * FPAD && scale.numel() == G * FPAD &&
+                pca_mean.numel() == G * FPAD &&
+                W.numel() == G * FPAD * FPAD,
+                op, ": one parameter set per group");
+    TORCH_CHECK(!cuts.is_cuda() && cuts.dtype() == at::kFloat &&
+                cuts.is_contiguous());
+    TORCH_CHECK(!cut_off.is_cuda() && cut_off.dtype() == at::kInt &&
+                cut_off.is_contiguous() &&
+                cut_off.numel() == G * (FPAD + 1));
+    const int* co = cut_off.data_ptr<int>();
+    auto cut_base = at::empty({G}, at::kInt);
+    long n_cuts = 0;
+    for (long g = 0; g < G; ++g, co += FPAD + 1) {
+        TORCH_CHECK(co[0] == 0, op, ": cut offsets of group ", g,
+                    " must start at 0");
+        for (int f = 0; f < FPAD; ++f)
+            TORCH_CHECK(co[f + 1] >= co[f] &&
+                        co[f + 1] - co[f] <= DETECT_MAX_CUTS,
+                        op, ": bad cut count for group ", g, " feature ", f);
+        cut_base.data_ptr<int>()[g] = (int)n_cuts;
+        n_cuts += co[FPAD];
+        TORCH_CHECK(n_cuts < (1L << 31));
+    }
+    TORCH_CHECK(n_cuts == cuts.numel(), op,
+                ": cut offsets do not cover the cut array");
+    return cut_base;
 }
 
 // detect_encode per group: rows seg_off[g]:seg_off[g+1] are encoded with
@@ -887,35 +935,9 @@ at::Tensor holdout_encode(at::Tensor X, at::Tensor seg_off, at::Tensor mean,
     auto tab = holdout_block_table(seg_off, M, DETECT_BLK, dev,
                                    "holdout_encode");
     const long G = seg_off.numel() - 1;
-    for (const at::Tensor* p : {&mean, &scale, &pca_mean, &W})
-        TORCH_CHECK(!p->is_cuda() && p->dtype() == at::kDouble &&
-                    p->is_contiguous());
-    TORCH_CHECK(mean.numel() == G * FPAD && scale.numel() == G * FPAD &&
-                pca_mean.numel() == G * FPAD &&
-                W.numel() == G * FPAD * FPAD,
-                "holdout_encode: one parameter set per group");
-    TORCH_CHECK(!cuts.is_cuda() && cuts.dtype() == at::kFloat &&
-                cuts.is_contiguous());
-    TORCH_CHECK(!cut_off.is_cuda() && cut_off.dtype() == at::kInt &&
-                cut_off.is_contiguous() &&
-                cut_off.numel() == G * (FPAD + 1));
-    const int* co = cut_off.data_ptr<int>();
-    auto cut_base = at::empty({G}, at::kInt);
-    long n_cuts = 0;
-    for (long g = 0; g < G; ++g, co += FPAD + 1) {
-        TORCH_CHECK(co[0] == 0, "holdout_encode: cut offsets of group ", g,
-                    " must start at 0");
-        for (int f = 0; f < FPAD; ++f)
-            TORCH_CHECK(co[f + 1] >= co[f] &&
-                        co[f + 1] - co[f] <= DETECT_MAX_CUTS,
-                        "holdout_encode: bad cut count for group ", g,
-                        " feature ", f);
-        cut_base.data_ptr<int>()[g] = (int)n_cuts;
-        n_cuts += co[FPAD];
-        TORCH_CHECK(n_cuts < (1L << 31));
-    }
-    TORCH_CHECK(n_cuts == cuts.numel(),
-                "holdout_encode: cut offsets do not cover the cut array");
+    auto cut_base = grouped_params_check(mean, scale, pca_mean, W, cuts,
+                                         cut_off, G, "holdout_encode");
+    const long n_cuts = cuts.numel();
 
     const at::cuda::OptionalCUDAGuard guard(dev);
     auto codes = at::empty({M, FPAD}, X.options().dtype(at::kByte));
@@ -1016,6 +1038,155 @@ std::vector<at::Tensor> threshold_counts(at::Tensor acc, at::Tensor labels,
     return {curve, argmax};
 }
 
+// ---------------------------------------------------------------------------
+// permutation importance (importance.hip)
+// ---------------------------------------------------------------------------
+// (counts int32 [J, R, G + 1, 3], baseline int32 [G + 1, 3]), columns FP,
+// FN, TP, row G pooled.  Job (j, r) classifies X with the columns of
+// masks[j] taken from row perm[r][i]; group g is served by detector
+// det_of_group[g] of the D stacked ones (the layout of holdout_encode and
+// holdout_proba, D in place of G).  threshold < 0 selects the argmax rule,
+// otherwise a row is predicted flaky iff acc1 / n_trees >= threshold.
+//
+// seg_off, det_of_group, masks, perm and the parameters arrive
+// CPU-resident.  perm is checked HERE, entry by entry, to stay inside the
+// row's own group, and uploaded afterwards: the kernel follows it
+// unchecked, so there is no device-resident form of the argument.
+std::vector<at::Tensor> permuted_counts(
+    at::Tensor X, at::Tensor labels, at::Tensor seg_off,
+    at::Tensor det_of_group, at::Tensor perm, at::Tensor masks,
+    at::Tensor mean, at::Tensor scale, at::Tensor pca_mean, at::Tensor W,
+    bool has_pca, at::Tensor cuts, at::Tensor cut_off, int64_t F,
+    at::Tensor tree_off, at::Tensor nodes_packed, int64_t n_trees,
+    double threshold) {
+    const char* op = "permuted_counts";
+    TORCH_CHECK(X.is_cuda() && X.dtype() == at::kDouble && X.dim() == 2 &&
+                X.size(1) == FPAD && X.is_contiguous());
+    TORCH_CHECK(F >= 1 && F <= FPAD);
+    const long M = X.size(0);
+    auto dev = X.device();
+    TORCH_CHECK(labels.is_cuda() && labels.dtype() == at::kByte &&
+                labels.dim() == 1 && labels.is_contiguous() &&
+                labels.numel() == M);
+    TORCH_CHECK(std::isfinite(threshold) || threshold < 0.0, op,
+                ": threshold must be finite (negative: argmax rule)");
+    TORCH_CHECK(!seg_off.is_cuda() && seg_off.dtype() == at::kInt &&
+                seg_off.dim() == 1 && seg_off.numel() >= 2, op,
+                ": seg_off must be CPU int32 [G+1]");
+    const long G = seg_off.numel() - 1;
+    TORCH_CHECK(mean.dim() == 2 && mean.size(0) >= 1, op,
+                ": parameters must be [D, 16]");
+    const long D = mean.size(0);
+    auto cut_base = grouped_params_check(mean, scale, pca_mean, W, cuts,
+                                         cut_off, D, op);
+    TORCH_CHECK(!det_of_group.is_cuda() && det_of_group.dtype() == at::kInt &&
+                det_of_group.dim() == 1 && det_of_group.is_contiguous() &&
+                det_of_group.numel() == G, op,
+                ": det_of_group must be CPU int32 [G]");
+    const int* det = det_of_group.data_ptr<int>();
+    for (long g = 0; g < G; ++g)
+        TORCH_CHECK(det[g] >= 0 && det[g] < D, op, ": group ", g,
+                    " names detector ", det[g], " of ", D);
+    auto tab = holdout_block_table(seg_off, M, IMPORTANCE_ROWS, dev, op, det);
+    auto tab_enc = holdout_block_table(seg_off, M, DETECT_BLK, dev, op, det,
+                                       true);
+    auto tab_acc = holdout_block_table(seg_off, M, HOLDOUT_PROBA_ROWS, dev,
+                                       op, det, true);
+
+    TORCH_CHECK(!masks.is_cuda() && masks.dtype() == at::kInt &&
+                masks.dim() == 1 && masks.is_contiguous() &&
+                masks.numel() >= 1, op, ": masks must be CPU int32 [J]");
+    const long J = masks.numel();
+    for (long j = 0; j < J; ++j) {
+        const int m = masks.data_ptr<int>()[j];
+        TORCH_CHECK(m > 0 && (m >> F) == 0, op, ": mask ", j,
+                    " must be non-zero and within the low F bits");
+    }
+    TORCH_CHECK(!perm.is_cuda() && perm.dtype() == at::kInt &&
+                perm.dim() == 2 && perm.is_contiguous() &&
+                perm.size(0) >= 1 && perm.size(1) == M, op,
+                ": perm must be CPU int32 [R, M]");
+    const long R = perm.size(0);
+    const int* so = seg_off.data_ptr<int>();
+    for (long r = 0; r < R; ++r) {
+        const int* pr = perm.data_ptr<int>() + r * M;
+        for (long g = 0; g < G; ++g)
+            for (int i = so[g]; i < so[g + 1]; ++i)
+                TORCH_CHECK(pr[i] >= so[g] && pr[i] < so[g + 1], op,
+                            ": perm[", r, "][", i,
+                            "] leaves the row's own group");
+    }
+    TORCH_CHECK(J * R * (G + 1) * 3 < (1L << 31), op, ": too many jobs");
+
+    TORCH_CHECK(tree_off.is_cuda() && tree_off.dtype() == at::kLong &&
+                tree_off.is_contiguous() && n_trees >= 1 &&
+                n_trees < (1L << 20) &&
+                tree_off.numel() == D * n_trees + 1, op,
+                ": n_trees root ids per detector and an end");
+    TORCH_CHECK(nodes_packed.is_cuda() && nodes_packed.dtype() == at::kInt &&
+                nodes_packed.dim() == 2 && nodes_packed.size(1) == 2 &&
+                nodes_packed.is_contiguous() &&
+                nodes_packed.size(0) < (1L << 31));
+
+    const at::cuda::OptionalCUDAGuard guard(dev);
+    auto opts = X.options().dtype(at::kInt);
+    // both outputs in one allocation, cleared by one memset
+    const long n_counts = J * R * (G + 1) * 3;
+    auto out = at::empty({n_counts + (G + 1) * 3}, opts);
+    hipStream_t s = current_stream();
+    TORCH_CHECK(hipMemsetAsync(out.data_ptr<int>(), 0,
+                               out.numel() * sizeof(int), s) == hipSuccess);
+    auto counts = out.narrow(0, 0, n_counts).view({J, R, G + 1, 3});
+    auto baseline = out.narrow(0, n_counts, (G + 1) * 3).view({G + 1, 3});
+    if (M == 0) return {counts, baseline};
+
+    auto mean_d = mean.to(dev), scale_d = scale.to(dev);
+    auto pmean_d = pca_mean.to(dev), W_d = W.to(dev);
+    auto cuts_d = cuts.to(dev), off_d = cut_off.to(dev);
+    auto base_d = cut_base.to(dev);
+    auto perm_d = perm.to(dev), masks_d = masks.to(dev);
+    const float* cuts_p = cuts.numel() ? cuts_d.data_ptr<float>() : nullptr;
+    const int n_blocks =
+        ((int)n_trees + PREDICT_TREE_BLOCK - 1) / PREDICT_TREE_BLOCK;
+
+    // the unpermuted rows, once: codes and (acc0, acc1) per row
+    auto codes = at::empty({M, FPAD}, X.options().dtype(at::kByte));
+    auto acc = at::empty({M, 2}, X.options());
+    holdout_encode_kernel<<<(int)tab_enc.size(0), DETECT_BLK, 0, s>>>(
+        X.data_ptr<double>(), (const int4*)tab_enc.data_ptr<int>(),
+        mean_d.data_ptr<double>(), scale_d.data_ptr<double>(),
+        pmean_d.data_ptr<double>(), W_d.data_ptr<double>(), has_pca ? 1 : 0,
+        cuts_p, off_d.data_ptr<int>(), base_d.data_ptr<int>(), (int)F,
+        codes.data_ptr<uint8_t>());
+    holdout_proba_kernel<<<(int)tab_acc.size(0), DETECT_BLK, 0, s>>>(
+        codes.data_ptr<uint8_t>(), (const int4*)tab_acc.data_ptr<int>(),
+        tree_off.data_ptr<long>(), (const int2*)nodes_packed.data_ptr<int>(),
+        (int)n_trees, n_blocks, (double2*)acc.data_ptr<double>());
+
+    // a wave per job: split the jobs over blockIdx.y until the grid holds
+    // about four waves per SIMD (256 CUs x 4 SIMDs), and never more
+    // shares than there are rounds of IMPORTANCE_WAVES jobs
+    const long n_jobs = J * R, nb = tab.size(0);
+    const long rounds = (n_jobs + IMPORTANCE_WAVES - 1) / IMPORTANCE_WAVES;
+    const long want = (1024 + nb - 1) / nb;
+    const dim3 grid((unsigned)nb,
+                    (unsigned)std::max(1L, std::min({rounds, want, 65535L})));
+    auto launch = has_pca ? permuted_counts_kernel<true>
+                          : permuted_counts_kernel<false>;
+    launch<<<grid, DETECT_BLK, 0, s>>>(
+        X.data_ptr<double>(), labels.data_ptr<uint8_t>(),
+        (const int4*)tab.data_ptr<int>(), codes.data_ptr<uint8_t>(),
+        (const double2*)acc.data_ptr<double>(), perm_d.data_ptr<int>(),
+        masks_d.data_ptr<int>(), mean_d.data_ptr<double>(),
+        scale_d.data_ptr<double>(), pmean_d.data_ptr<double>(),
+        W_d.data_ptr<double>(), cuts_p, off_d.data_ptr<int>(),
+        base_d.data_ptr<int>(), (int)F, tree_off.data_ptr<long>(),
+        (const int2*)nodes_packed.data_ptr<int>(), (int)n_trees, n_blocks,
+        (int)n_jobs, (int)R, (int)M, (int)G, threshold,
+        counts.data_ptr<int>(), baseline.data_ptr<int>());
+    return {counts, baseline};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("treeshap", &treeshap, py::call_guard<py::gil_scoped_release>(),
           "Path-dependent TreeSHAP (class-0), summed over trees");
@@ -1070,4 +1241,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("threshold_counts", &threshold_counts,
           py::call_guard<py::gil_scoped_release>(),
           "Per-group [FP, FN, TP] under argmax and K probability thresholds");
+    m.def("permuted_counts", &permuted_counts,
+          py::call_guard<py::gil_scoped_release>(),
+          "Per-group [FP, FN, TP] of J column masks x R row permutations");
 }

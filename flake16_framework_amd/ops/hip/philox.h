@@ -18,6 +18,7 @@
 #define TAG_THRESH 3u
 #define TAG_SMOTE_PICK 4u
 #define TAG_SMOTE_GAP 5u
+#define TAG_PERMUTE 6u     // drawn on the host only (engine/importance.py)
 
 struct Philox4 {
     uint32_t x0, x1, x2, x3;

@@ -28,6 +28,7 @@ TAG_FEATSEL = 2     # per-node feature-subset permutation
 TAG_THRESH = 3      # Extra-Trees random threshold draws
 TAG_SMOTE_PICK = 4  # SMOTE (row, neighbor) selection
 TAG_SMOTE_GAP = 5   # SMOTE interpolation gap
+TAG_PERMUTE = 6     # importance: within-project row permutation (host only)
 
 
 def philox4x32(c0, c1, c2, c3, k0, k1):
