@@ -56,6 +56,20 @@ GPU/synthetic extensions:
                              project first (as `holdout` does) and scores
                              every project with the detector that never
                              saw it
+  similar [--detector F] [--tests-file F] [--corpus F] [--out F] [--k K]
+      [--flaky-only] [--keep-self] [--backend B]
+                             forest proximity: for every test of the
+                             tests file the K (1..16, default 5) tests of
+                             the labelled corpus (default tests.json) that
+                             share a leaf with it in the most trees, ties
+                             to the earlier corpus test -> similar.json
+                             {"k", "n_trees", "corpus_tests", "tests":
+                             {proj: {nodeid: [proba, pred, [[corpus_proj,
+                             corpus_nodeid, label, shared], ...]]}}}.
+                             --flaky-only ranks the flaky corpus tests
+                             only; a test found in the corpus under its
+                             own (project, nodeid) is left out unless
+                             --keep-self is given
 
 Distributed: launch via `python -m torch.distributed.run --nproc-per-node N
 experiment.py scores` — one rank per GPU over RCCL; rank 0 writes the
@@ -241,6 +255,33 @@ def main(argv=None):
               f"{', leave-one-project-out' if leave_out else ''}; "
               f"baseline F1 {fmt(res['baseline']['total'][5])}; "
               f"largest mean F1 drop: {top})")
+    elif command == "similar":
+        from .constants import DETECTOR_FILE, SIMILAR_FILE, TESTS_FILE
+        from .engine.detector import Detector
+        from .engine.similar import MAX_K, write_similar
+        detector_file = _pop_flag(args, "--detector", DETECTOR_FILE)
+        tests_file = _pop_flag(args, "--tests-file", TESTS_FILE)
+        corpus = _pop_flag(args, "--corpus", TESTS_FILE)
+        out = _pop_flag(args, "--out", SIMILAR_FILE)
+        k = int(_pop_flag(args, "--k", "5"))
+        if not 1 <= k <= MAX_K:
+            raise ValueError(f"--k takes 1..{MAX_K}")
+        flaky_only = _pop_flag(args, "--flaky-only", False, boolean=True)
+        keep_self = _pop_flag(args, "--keep-self", False, boolean=True)
+        backend = _pop_flag(args, "--backend", "auto")
+        res = write_similar(Detector.load(detector_file),
+                            tests_file=tests_file, corpus=corpus,
+                            out_file=out, k=k, flaky_only=flaky_only,
+                            skip_self=not keep_self, backend=backend)
+        first = res["idx"][:, 0]
+        flagged = (res["pred"] == 1) & (first >= 0)
+        n_flagged = int((res["pred"] == 1).sum())
+        hits = int(res["corpus_labels"][first[flagged]].sum())
+        share = "n/a" if n_flagged == 0 else f"{hits / n_flagged:.4f}"
+        print(f"wrote {out} ({len(res['pred'])} tests against "
+              f"{res['n_candidates']} corpus tests, k {res['k']}; "
+              f"{n_flagged} predicted flaky, first neighbour labelled "
+              f"flaky for {share} of them)")
     elif command == "figures":
         offline = _pop_flag(args, "--offline", False, boolean=True)
         from .report.figures import write_figures

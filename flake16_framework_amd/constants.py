@@ -20,6 +20,7 @@ DETECTIONS_FILE = "detections.json"
 EXPLANATIONS_FILE = "explanations.json"
 HOLDOUT_FILE = "holdout.json"
 IMPORTANCE_FILE = "importance.json"
+SIMILAR_FILE = "similar.json"
 SUBJECTS_FILE = "subjects.txt"
 REQUIREMENTS_FILE = "requirements.txt"
 

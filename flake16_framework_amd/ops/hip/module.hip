@@ -17,6 +17,7 @@
 #include "explain.hip"
 #include "holdout.hip"
 #include "importance.hip"
+#include "similar.hip"
 
 #include <vector>
 #include <algorithm>
@@ -1187,6 +1188,162 @@ std::vector<at::Tensor> permuted_counts(
     return {counts, baseline};
 }
 
+// ---------------------------------------------------------------------------
+// forest proximity (similar.hip)
+// ---------------------------------------------------------------------------
+// Tree-local canonical leaf ids as int32 [M, T].  The caller guarantees a
+// well-formed packed forest, as for forest_proba.
+at::Tensor forest_leaves(at::Tensor codes, at::Tensor tree_off,
+                         at::Tensor nodes_packed, int64_t n_trees) {
+    const char* op = "forest_leaves";
+    TORCH_CHECK(codes.is_cuda() && codes.dtype() == at::kByte &&
+                codes.dim() == 2 && codes.size(1) == FPAD &&
+                codes.is_contiguous(), op,
+                ": codes must be device uint8 [M, 16]");
+    TORCH_CHECK(tree_off.is_cuda() && tree_off.dtype() == at::kLong &&
+                tree_off.is_contiguous() && n_trees >= 1 &&
+                n_trees <= PROX_MAX_T && tree_off.numel() == n_trees + 1,
+                op, ": n_trees root ids and an end");
+    TORCH_CHECK(nodes_packed.is_cuda() && nodes_packed.dtype() == at::kInt &&
+                nodes_packed.dim() == 2 && nodes_packed.size(1) == 2 &&
+                nodes_packed.is_contiguous() &&
+                nodes_packed.size(0) < (1L << 31), op,
+                ": nodes must be device int32 [n_nodes, 2]");
+    TORCH_CHECK(codes.device() == tree_off.device() &&
+                codes.device() == nodes_packed.device(), op,
+                ": tensors on different devices");
+    const at::cuda::OptionalCUDAGuard guard(codes.device());
+    const long M = codes.size(0);
+    TORCH_CHECK(M < (1L << 31));
+    auto leaf = at::empty({M, n_trees}, codes.options().dtype(at::kInt));
+    if (M == 0) return leaf;
+    const long total = M * n_trees;
+    const long blocks = (total + DETECT_BLK - 1) / DETECT_BLK;
+    TORCH_CHECK(blocks < (1L << 31), op, ": too many (row, tree) pairs");
+    forest_leaves_kernel<<<(unsigned)blocks, DETECT_BLK, 0,
+                           current_stream()>>>(
+        codes.data_ptr<uint8_t>(), tree_off.data_ptr<long>(),
+        (const int2*)nodes_packed.data_ptr<int>(), (int)M, (int)n_trees,
+        leaf.data_ptr<int>());
+    return leaf;
+}
+
+template <int K, bool PACKED>
+static void launch_proximity(dim3 grid, hipStream_t s, const uint32_t* qT,
+                             const uint32_t* cP, const int* self, int M,
+                             int N, int T, int W, int chunk_rows, int k,
+                             int* o_idx, int* o_sh) {
+    proximity_topk_kernel<K, PACKED><<<grid, PROX_BLK, 0, s>>>(
+        qT, cP, self, M, N, T, W, chunk_rows, k, o_idx, o_sh);
+}
+
+// For every row of leaf_q the first k rows of leaf_c in the order (more
+// equal ids, then lower row), leaving out row self_idx[q] (-1: none):
+// (idx, shared), both int32 [M, k], short lists padded with (-1, 0).
+// self_idx may live on either side; it is range-checked on the host.
+std::vector<at::Tensor> proximity_topk(at::Tensor leaf_q, at::Tensor leaf_c,
+                                       at::Tensor self_idx, int64_t k) {
+    const char* op = "proximity_topk";
+    for (const at::Tensor* p : {&leaf_q, &leaf_c})
+        TORCH_CHECK(p->is_cuda() && p->dtype() == at::kInt &&
+                    p->dim() == 2 && p->is_contiguous(), op,
+                    ": leaf ids must be contiguous device int32 [rows, T]");
+    TORCH_CHECK(leaf_q.device() == leaf_c.device(), op,
+                ": leaf matrices on different devices");
+    const long M = leaf_q.size(0), N = leaf_c.size(0), T = leaf_q.size(1);
+    TORCH_CHECK(leaf_c.size(1) == T, op, ": query rows hold ", T,
+                " trees, corpus rows ", leaf_c.size(1));
+    TORCH_CHECK(T >= 1 && T <= PROX_MAX_T, op, ": T must be in 1..",
+                PROX_MAX_T);
+    TORCH_CHECK(k >= 1 && k <= PROX_MAX_K, op, ": k must be in 1..",
+                PROX_MAX_K);
+    TORCH_CHECK(M < (1L << 31) && N < (1L << 31) - PROX_CHUNK, op,
+                ": too many rows");
+    TORCH_CHECK(self_idx.dtype() == at::kInt && self_idx.dim() == 1 &&
+                self_idx.size(0) == M, op, ": self_idx must be int32 [M]");
+    auto self_host = self_idx.cpu().contiguous();
+    for (long q = 0; q < M; ++q) {
+        const int v = self_host.data_ptr<int>()[q];
+        TORCH_CHECK(v >= -1 && v < N, op, ": self_idx[", q, "] = ", v,
+                    " is outside [-1, ", N, ")");
+    }
+
+    const at::cuda::OptionalCUDAGuard guard(leaf_q.device());
+    auto opts = leaf_q.options();
+    auto idx = at::empty({M, k}, opts), shared = at::empty({M, k}, opts);
+    if (M == 0) return {idx, shared};
+    if (N == 0) {
+        idx.fill_(-1);
+        shared.zero_();
+        return {idx, shared};
+    }
+    hipStream_t s = current_stream();
+    auto self_d = self_host.to(leaf_q.device());
+
+    // do all ids fit 16 bits?  one pass and one 4-byte readback
+    auto flag = at::zeros({1}, opts);
+    for (const at::Tensor* p : {&leaf_q, &leaf_c}) {
+        const long n = p->numel();
+        const long blocks =
+            std::min(2048L, (n + PROX_BLK - 1) / PROX_BLK);
+        prox_wide_kernel<<<(unsigned)blocks, PROX_BLK, 0, s>>>(
+            p->data_ptr<int>(), n, flag.data_ptr<int>());
+    }
+    const bool packed = flag.cpu().data_ptr<int>()[0] == 0;
+
+    const long per = packed ? 2 : 1;
+    const long W = ((T + per - 1) / per + PROX_D - 1) / PROX_D * PROX_D;
+    auto qT = at::empty({W, M}, opts), cP = at::empty({N, W}, opts);
+    auto pack = packed ? prox_pack_kernel<true> : prox_pack_kernel<false>;
+    TORCH_CHECK((M * W + PROX_BLK - 1) / PROX_BLK < (1L << 31) &&
+                (N * W + PROX_BLK - 1) / PROX_BLK < (1L << 31), op,
+                ": too many ids");
+    pack<<<(unsigned)((M * W + PROX_BLK - 1) / PROX_BLK), PROX_BLK, 0, s>>>(
+        leaf_q.data_ptr<int>(), M, (int)T, (int)W, 1L, M,
+        (uint32_t*)qT.data_ptr<int>());
+    pack<<<(unsigned)((N * W + PROX_BLK - 1) / PROX_BLK), PROX_BLK, 0, s>>>(
+        leaf_c.data_ptr<int>(), N, (int)T, (int)W, W, 1L,
+        (uint32_t*)cP.data_ptr<int>());
+
+    // Chunks of PROX_CHUNK corpus rows; of a whole multiple of that once
+    // the grid would pass 2048 workgroups (8 per CU), so the partial
+    // lists stay a small multiple of the output.
+    const long q_blocks = (M + PROX_BLK - 1) / PROX_BLK;
+    const long most = std::min(65535L, std::max(1L, 2048 / q_blocks));
+    const long n_least = (N + PROX_CHUNK - 1) / PROX_CHUNK;
+    const long chunk_rows = PROX_CHUNK * ((n_least + most - 1) / most);
+    const long n_chunks = (N + chunk_rows - 1) / chunk_rows;
+
+    at::Tensor p_idx = idx, p_sh = shared;
+    if (n_chunks > 1) {
+        p_idx = at::empty({n_chunks, k, M}, opts);
+        p_sh = at::empty({n_chunks, k, M}, opts);
+    }
+    const int kmax = k == 1 ? 1 : (k <= 8 ? 8 : 16);
+    auto launch =
+        kmax == 1 ? (packed ? launch_proximity<1, true>
+                            : launch_proximity<1, false>)
+        : kmax == 8 ? (packed ? launch_proximity<8, true>
+                              : launch_proximity<8, false>)
+                    : (packed ? launch_proximity<16, true>
+                              : launch_proximity<16, false>);
+    launch(dim3((unsigned)q_blocks, (unsigned)n_chunks), s,
+           (const uint32_t*)qT.data_ptr<int>(),
+           (const uint32_t*)cP.data_ptr<int>(), self_d.data_ptr<int>(),
+           (int)M, (int)N, (int)T, (int)W, (int)chunk_rows, (int)k,
+           p_idx.data_ptr<int>(), p_sh.data_ptr<int>());
+    if (n_chunks > 1) {
+        auto merge = kmax == 1 ? proximity_merge_kernel<1>
+                     : kmax == 8 ? proximity_merge_kernel<8>
+                                 : proximity_merge_kernel<16>;
+        merge<<<(unsigned)q_blocks, PROX_BLK, 0, s>>>(
+            p_idx.data_ptr<int>(), p_sh.data_ptr<int>(), (int)M,
+            (int)n_chunks, (int)k, idx.data_ptr<int>(),
+            shared.data_ptr<int>());
+    }
+    return {idx, shared};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("treeshap", &treeshap, py::call_guard<py::gil_scoped_release>(),
           "Path-dependent TreeSHAP (class-0), summed over trees");
@@ -1244,4 +1401,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("permuted_counts", &permuted_counts,
           py::call_guard<py::gil_scoped_release>(),
           "Per-group [FP, FN, TP] of J column masks x R row permutations");
+    m.def("forest_leaves", &forest_leaves,
+          py::call_guard<py::gil_scoped_release>(),
+          "Per-row, per-tree canonical leaf ids over a packed forest");
+    m.def("proximity_topk", &proximity_topk,
+          py::call_guard<py::gil_scoped_release>(),
+          "First k corpus rows by shared leaves, ties to the lower row");
 }

@@ -31,6 +31,7 @@ setup(
                      "flake16_framework_amd/ops/hip/explain.hip",
                      "flake16_framework_amd/ops/hip/holdout.hip",
                      "flake16_framework_amd/ops/hip/importance.hip",
+                     "flake16_framework_amd/ops/hip/similar.hip",
                      "flake16_framework_amd/ops/hip/philox.h",
                      "flake16_framework_amd/ops/hip/wave_ops.h"],
             extra_compile_args={
