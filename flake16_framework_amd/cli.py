@@ -30,7 +30,19 @@ GPU/synthetic extensions:
                              {"feature_names", "base_value", "tests":
                              {proj: {nodeid: [proba, pred, phi...]}}};
                              class-1 values, the negation of shap.pkl's
-  holdout [--config nod|od] [--keys K0 K1 K2 K3 K4] [--backend B]
+  interact [--detector F] [--tests-file F] [--out F] [--top N]
+      [--matrix-out F] [--backend B]
+                             explain plus SHAP interaction values: every
+                             test's probability split into an [F, F]
+                             matrix whose row g sums to phi[g] ->
+                             interactions.json {"feature_names",
+                             "base_value", "mean_abs", "pairs", "tests":
+                             {proj: {nodeid: [proba, pred, [diagonal],
+                             [[g, f, Phi[g,f] + Phi[f,g]], ...]]}}} with
+                             the N (default 3) strongest pairs per test;
+                             --matrix-out saves the full [M, F, F] array
+                             as .npy
+  holdout[--config nod|od] [--keys K0 K1 K2 K3 K4] [--backend B]
       [--tests-file F] [--out F] [--n-trees N] [--thresholds K]
       [--detections F]
                              leave-one-project-out evaluation: every
@@ -180,6 +192,30 @@ def main(argv=None):
                         for f in np.argsort(-weight, kind="stable")[:3])
         print(f"wrote {out} ({len(res['pred'])} tests; "
               f"largest mean |phi|: {top})")
+    elif command == "interact":
+        from .constants import DETECTOR_FILE, INTERACTIONS_FILE, TESTS_FILE
+        from .engine.detector import Detector
+        from .engine.interact import (
+            pair_index, rank_pairs, summarize, write_interactions,
+        )
+        detector_file = _pop_flag(args, "--detector", DETECTOR_FILE)
+        tests_file = _pop_flag(args, "--tests-file", TESTS_FILE)
+        out = _pop_flag(args, "--out", INTERACTIONS_FILE)
+        top = int(_pop_flag(args, "--top", "3"))
+        matrix_out = _pop_flag(args, "--matrix-out", None)
+        backend = _pop_flag(args, "--backend", "auto")
+        res = write_interactions(Detector.load(detector_file),
+                                 tests_file=tests_file, out_file=out,
+                                 top=top, matrix_out=matrix_out,
+                                 backend=backend)
+        names = res["feature_names"]
+        pairs = pair_index(len(names))
+        _, weight = summarize(res["interactions"])
+        best = ", ".join(
+            f"{names[pairs[p, 0]]} x {names[pairs[p, 1]]} {weight[p]:.4f}"
+            for p in rank_pairs(weight)[:3])
+        print(f"wrote {out} ({len(res['pred'])} tests; "
+              f"largest mean |Phi[g,f] + Phi[f,g]|: {best})")
     elif command == "holdout":
         from .configgrid import SHAP_CONFIGS
         from .constants import HOLDOUT_FILE, TESTS_FILE

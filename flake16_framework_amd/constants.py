@@ -21,6 +21,7 @@ EXPLANATIONS_FILE = "explanations.json"
 HOLDOUT_FILE = "holdout.json"
 IMPORTANCE_FILE = "importance.json"
 SIMILAR_FILE = "similar.json"
+INTERACTIONS_FILE = "interactions.json"
 SUBJECTS_FILE = "subjects.txt"
 REQUIREMENTS_FILE = "requirements.txt"
 

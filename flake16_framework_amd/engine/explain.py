@@ -165,17 +165,24 @@ def device_shap(ops, codes, table, n_trees, F):
                              table["elem_code"], table["elem_z"], n_trees, F)
 
 
-def _explain_hip(detector, paths, X):
-    from ..ops.backend import get_ops
-
-    ops = get_ops()
+def explain_device(ops, detector, paths, X):
+    """The device part of explain: (codes, path table, acc [M, 2],
+    phi [M, 16]), all resident."""
     d = device_inputs(detector, X)
     codes = ops.detect_encode(d["X64"], d["mean"], d["scale"], d["pca_mean"],
                               d["W"], d["has_pca"], d["cuts"], d["cut_off"],
                               d["F"])
     acc = ops.forest_proba(codes, d["tree_off"], d["nodes"], d["n_trees"])
-    phi = device_shap(ops, codes, device_table(paths, codes.device),
-                      detector.n_trees, detector.n_features)
+    table = device_table(paths, codes.device)
+    phi = device_shap(ops, codes, table, detector.n_trees,
+                      detector.n_features)
+    return codes, table, acc, phi
+
+
+def _explain_hip(detector, paths, X):
+    from ..ops.backend import get_ops
+
+    _, _, acc, phi = explain_device(get_ops(), detector, paths, X)
     acc = acc.cpu().numpy()
     return acc[:, 0], acc[:, 1], phi.cpu().numpy()[:, :detector.n_features]
 
@@ -187,6 +194,17 @@ def _explain_ref(detector, paths, X):
     return acc0, acc1, shap_ref(detector, paths, codes)
 
 
+def input_rows(detector, tests=None, tests_file=None):
+    """(X, projects, nodeids) of a tests.json, which may hold no test."""
+    if tests is None:
+        tests = load_tests(tests_file)
+    if any(len(tests_proj) for tests_proj in tests.values()):
+        return load_rows(detector, tests, None)
+    # load_rows cannot shape an empty matrix
+    none = np.array([], dtype=str)
+    return np.zeros((0, detector.n_features)), none, none
+
+
 def explain(detector, tests=None, tests_file=None, backend="auto"):
     """detect() plus attributions for every test of a tests.json.
 
@@ -195,13 +213,7 @@ def explain(detector, tests=None, tests_file=None, backend="auto"):
     backend = _resolve_backend(backend)
     detector.validate()
     paths = build_merged_paths(detector)
-    if tests is None:
-        tests = load_tests(tests_file)
-    if any(len(tests_proj) for tests_proj in tests.values()):
-        X, projects, nodeids = load_rows(detector, tests, None)
-    else:       # load_rows cannot shape an empty matrix
-        X = np.zeros((0, detector.n_features))
-        projects = nodeids = np.array([], dtype=str)
+    X, projects, nodeids = input_rows(detector, tests, tests_file)
     if len(X) == 0:
         acc0 = acc1 = np.zeros(0)
         phi = np.zeros((0, detector.n_features))

@@ -15,6 +15,7 @@
 #include "treeshap.hip"
 #include "detect.hip"
 #include "explain.hip"
+#include "interact.hip"
 #include "holdout.hip"
 #include "importance.hip"
 #include "similar.hip"
@@ -769,20 +770,22 @@ at::Tensor forest_proba(at::Tensor codes, at::Tensor tree_off,
 // ---------------------------------------------------------------------------
 // saved-detector TreeSHAP (explain.hip)
 // ---------------------------------------------------------------------------
-// Class-1 attributions as float64 [M, FPAD] (columns >= F are zero) from
-// the codes of detect_encode and the merged-path table of
-// models/mergedpaths.py, all device-resident.  Everything the kernel
-// indexes with is checked here, on the device, with one readback.
-at::Tensor detector_shap(at::Tensor codes, at::Tensor tree_leaf_off,
-                         at::Tensor leaf_off, at::Tensor leaf_val,
-                         at::Tensor elem_code, at::Tensor elem_z,
-                         int64_t n_trees, int64_t F) {
+// The checks the ops over the merged-path table share: shapes and dtypes
+// on the host, then (when there are rows) everything a kernel indexes
+// with, on the device, with one readback.
+static void check_path_table(const char* op, const at::Tensor& codes,
+                             const at::Tensor& tree_leaf_off,
+                             const at::Tensor& leaf_off,
+                             const at::Tensor& leaf_val,
+                             const at::Tensor& elem_code,
+                             const at::Tensor& elem_z, int64_t n_trees,
+                             int64_t F) {
     TORCH_CHECK(codes.is_cuda() && codes.dtype() == at::kByte &&
                 codes.dim() == 2 && codes.size(1) == FPAD &&
                 codes.is_contiguous());
     TORCH_CHECK(F >= 1 && F <= FPAD);
-    TORCH_CHECK(n_trees >= 1 && n_trees <= 65535,
-                "detector_shap: tree count out of range");
+    TORCH_CHECK(n_trees >= 1 && n_trees <= 65535, op,
+                ": tree count out of range");
     for (const at::Tensor* p : {&tree_leaf_off, &leaf_off, &elem_code})
         TORCH_CHECK(p->is_cuda() && p->dtype() == at::kInt &&
                     p->dim() == 1 && p->is_contiguous());
@@ -793,17 +796,14 @@ at::Tensor detector_shap(at::Tensor codes, at::Tensor tree_leaf_off,
     TORCH_CHECK(tree_leaf_off.numel() == n_trees + 1 &&
                 leaf_off.numel() == L + 1 && elem_code.numel() == E &&
                 L >= n_trees && L < (1L << 31) && E < (1L << 31),
-                "detector_shap: path table sizes");
-    const long M = codes.size(0);
-    TORCH_CHECK(M < (1L << 31));
-
-    const at::cuda::OptionalCUDAGuard guard(codes.device());
-    auto phi = at::empty({M, FPAD}, codes.options().dtype(at::kDouble));
-    if (M == 0) return phi;
+                op, ": path table sizes");
+    TORCH_CHECK(codes.size(0) < (1L << 31));
+    if (codes.size(0) == 0) return;
 
     // offsets start at 0, end at the array they index and never step
     // back; a tree owns a leaf, a leaf at most F elements, and every
     // element names a feature below F
+    const at::cuda::OptionalCUDAGuard guard(codes.device());
     auto t_step = tree_leaf_off.diff();
     auto l_step = leaf_off.diff();
     auto ok = tree_leaf_off[0].eq(0) & tree_leaf_off[n_trees].eq(L) &
@@ -811,7 +811,23 @@ at::Tensor detector_shap(at::Tensor codes, at::Tensor tree_leaf_off,
               leaf_off[L].eq(E) & l_step.ge(0).all() & l_step.le(F).all();
     if (E > 0)
         ok = ok & elem_code.bitwise_and(0xFF).lt(F).all();
-    TORCH_CHECK(ok.item<bool>(), "detector_shap: malformed path table");
+    TORCH_CHECK(ok.item<bool>(), op, ": malformed path table");
+}
+
+// Class-1 attributions as float64 [M, FPAD] (columns >= F are zero) from
+// the codes of detect_encode and the merged-path table of
+// models/mergedpaths.py, all device-resident.
+at::Tensor detector_shap(at::Tensor codes, at::Tensor tree_leaf_off,
+                         at::Tensor leaf_off, at::Tensor leaf_val,
+                         at::Tensor elem_code, at::Tensor elem_z,
+                         int64_t n_trees, int64_t F) {
+    check_path_table("detector_shap", codes, tree_leaf_off, leaf_off,
+                     leaf_val, elem_code, elem_z, n_trees, F);
+    const long M = codes.size(0), E = elem_z.numel();
+
+    const at::cuda::OptionalCUDAGuard guard(codes.device());
+    auto phi = at::empty({M, FPAD}, codes.options().dtype(at::kDouble));
+    if (M == 0) return phi;
 
     // workspace [T, FPAD, rows] bounded at 256 MiB: rows go in chunks
     const long ws_cap = 256L << 20;
@@ -837,6 +853,56 @@ at::Tensor detector_shap(at::Tensor codes, at::Tensor tree_leaf_off,
             phi.data_ptr<double>());
     }
     return phi;
+}
+
+// ---------------------------------------------------------------------------
+// saved-detector SHAP interaction values (interact.hip)
+// ---------------------------------------------------------------------------
+// Class-1 interaction values as float64 [M, FPAD, FPAD] (rows and columns
+// >= F are zero) from the inputs of detector_shap and its output phi.
+at::Tensor detector_shap_interactions(
+    at::Tensor codes, at::Tensor tree_leaf_off, at::Tensor leaf_off,
+    at::Tensor leaf_val, at::Tensor elem_code, at::Tensor elem_z,
+    at::Tensor phi, int64_t n_trees, int64_t F) {
+    check_path_table("detector_shap_interactions", codes, tree_leaf_off,
+                     leaf_off, leaf_val, elem_code, elem_z, n_trees, F);
+    const long M = codes.size(0), E = elem_z.numel();
+    TORCH_CHECK(phi.is_cuda() && phi.device() == codes.device() &&
+                phi.dtype() == at::kDouble && phi.dim() == 2 &&
+                phi.size(0) == M && phi.size(1) == FPAD &&
+                phi.is_contiguous(),
+                "detector_shap_interactions: phi is detector_shap's "
+                "float64 [M, 16] on the device of codes");
+
+    const at::cuda::OptionalCUDAGuard guard(codes.device());
+    auto out = at::zeros({M, FPAD, FPAD}, codes.options().dtype(at::kDouble));
+    if (M == 0) return out;
+
+    // workspace [T, F, FPAD, rows] bounded at 256 MiB: rows go in chunks
+    const long ws_cap = 256L << 20;
+    const long per_row = n_trees * F * FPAD * (long)sizeof(double);
+    long chunk = std::max<long>(EXPLAIN_BLK,
+                                ws_cap / per_row / EXPLAIN_BLK * EXPLAIN_BLK);
+    chunk = std::min(chunk, M);
+    auto partial = at::empty({n_trees * F * FPAD * chunk},
+                             codes.options().dtype(at::kDouble));
+    hipStream_t s = current_stream();
+    for (long row0 = 0; row0 < M; row0 += chunk) {
+        const int mc = (int)std::min(chunk, M - row0);
+        const int gx = (mc + EXPLAIN_BLK - 1) / EXPLAIN_BLK;
+        detector_interact_tree_kernel<<<dim3(gx, (int)n_trees, (int)F),
+                                        EXPLAIN_BLK, 0, s>>>(
+            codes.data_ptr<uint8_t>(), tree_leaf_off.data_ptr<int>(),
+            leaf_off.data_ptr<int>(), leaf_val.data_ptr<double>(),
+            E ? elem_code.data_ptr<int>() : nullptr,
+            E ? elem_z.data_ptr<double>() : nullptr, (int)row0, mc,
+            partial.data_ptr<double>());
+        detector_interact_combine_kernel<<<dim3(gx, (int)F), EXPLAIN_BLK, 0,
+                                           s>>>(
+            partial.data_ptr<double>(), phi.data_ptr<double>(), (int)row0,
+            mc, (int)n_trees, out.data_ptr<double>());
+    }
+    return out;
 }
 
 // ---------------------------------------------------------------------------
@@ -1389,6 +1455,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("detector_shap", &detector_shap,
           py::call_guard<py::gil_scoped_release>(),
           "Per-row class-1 TreeSHAP over a detector's merged leaf paths");
+    m.def("detector_shap_interactions", &detector_shap_interactions,
+          py::call_guard<py::gil_scoped_release>(),
+          "Per-row class-1 SHAP interaction values over merged leaf paths");
     m.def("holdout_encode", &holdout_encode,
           py::call_guard<py::gil_scoped_release>(),
           "detect_encode with per-group parameters and cuts");
