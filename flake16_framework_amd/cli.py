@@ -82,6 +82,23 @@ GPU/synthetic extensions:
                              only; a test found in the corpus under its
                              own (project, nodeid) is left out unless
                              --keep-self is given
+  dependence [--detector F] [--tests-file F] [--out F] [--grid V]
+      [--threshold T] [--ice-out F.npy] [--backend B]
+                             partial dependence: every raw feature of the
+                             detector is set, in all tests at once, to
+                             each of up to V (2..64, default 20) values
+                             between its 5th and 95th percentile, and the
+                             tests are classified again ->
+                             dependence.json {"config_keys", "rule",
+                             "threshold", "n_tests", "baseline", "features":
+                             {name: {"grid", "mean_proba", "flagged",
+                             "range", "projects": {proj: {"mean_proba",
+                             "flagged"}}}}}: the mean flaky probability
+                             and the number of tests predicted flaky
+                             (argmax, or proba >= T with --threshold) at
+                             every grid value, pooled and per project.
+                             --ice-out saves the per-test curves as a
+                             float64 [tests, jobs] .npy
 
 Distributed: launch via `python -m torch.distributed.run --nproc-per-node N
 experiment.py scores` — one rank per GPU over RCCL; rank 0 writes the
@@ -318,6 +335,33 @@ def main(argv=None):
               f"{res['n_candidates']} corpus tests, k {res['k']}; "
               f"{n_flagged} predicted flaky, first neighbour labelled "
               f"flaky for {share} of them)")
+    elif command == "dependence":
+        from .constants import DEPENDENCE_FILE, DETECTOR_FILE, TESTS_FILE
+        from .engine.dependence import write_dependence
+        from .engine.detector import Detector
+        detector_file = _pop_flag(args, "--detector", DETECTOR_FILE)
+        tests_file = _pop_flag(args, "--tests-file", TESTS_FILE)
+        out = _pop_flag(args, "--out", DEPENDENCE_FILE)
+        grid = int(_pop_flag(args, "--grid", "20"))
+        threshold = _pop_flag(args, "--threshold", None)
+        ice_out = _pop_flag(args, "--ice-out", None)
+        backend = _pop_flag(args, "--backend", "auto")
+        res = write_dependence(
+            Detector.load(detector_file), tests_file=tests_file,
+            out_file=out, ice_out=ice_out, grid=grid,
+            threshold=None if threshold is None else float(threshold),
+            backend=backend)
+        # largest first; ties keep the features' order
+        spans = sorted(((name, entry["range"])
+                        for name, entry in res["features"].items()),
+                       key=lambda s: -s[1])
+        top = ", ".join(f"{name} {v:.4f}" for name, v in spans[:3])
+        n_jobs = sum(len(e["grid"]) for e in res["features"].values())
+        print(f"wrote {out} ({res['n_tests']} tests, "
+              f"{len(res['features'])} features, {n_jobs} grid values, "
+              f"{res['rule']} rule; baseline mean probability "
+              f"{res['baseline']['mean_proba']:.4f}; "
+              f"largest range of the mean probability: {top})")
     elif command == "figures":
         offline = _pop_flag(args, "--offline", False, boolean=True)
         from .report.figures import write_figures

@@ -22,6 +22,7 @@ HOLDOUT_FILE = "holdout.json"
 IMPORTANCE_FILE = "importance.json"
 SIMILAR_FILE = "similar.json"
 INTERACTIONS_FILE = "interactions.json"
+DEPENDENCE_FILE = "dependence.json"
 SUBJECTS_FILE = "subjects.txt"
 REQUIREMENTS_FILE = "requirements.txt"
 

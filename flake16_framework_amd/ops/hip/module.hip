@@ -18,6 +18,7 @@
 #include "interact.hip"
 #include "holdout.hip"
 #include "importance.hip"
+#include "dependence.hip"
 #include "similar.hip"
 
 #include <vector>
@@ -1255,6 +1256,159 @@ std::vector<at::Tensor> permuted_counts(
 }
 
 // ---------------------------------------------------------------------------
+// partial dependence and ICE (dependence.hip)
+// ---------------------------------------------------------------------------
+// (S fp64 [J + 1, G + 1], flagged int32 [J + 1, G + 1], ice fp64 [J, M] or
+// an empty tensor).  Job j classifies X with column job_col[j] of every
+// row set to job_val[j]; row J is the unmodified X.  S[j][g] is the sum of
+// acc1 over group g in the reduction order pinned in dependence.hip,
+// flagged[j][g] the rows predicted flaky, column G pooled; ice[j][i] is
+// acc1 of row i under job j.  threshold < 0 selects the argmax rule,
+// otherwise a row is predicted flaky iff acc1 / n_trees >= threshold.
+//
+// One detector serves every group: the parameters are one set in the
+// stacked layout of holdout_encode (D = 1).  seg_off, the jobs and the
+// parameters arrive CPU-resident and are checked here.
+std::vector<at::Tensor> partial_dependence(
+    at::Tensor X, at::Tensor seg_off, at::Tensor job_col, at::Tensor job_val,
+    at::Tensor mean, at::Tensor scale, at::Tensor pca_mean, at::Tensor W,
+    bool has_pca, at::Tensor cuts, at::Tensor cut_off, int64_t F,
+    at::Tensor tree_off, at::Tensor nodes_packed, int64_t n_trees,
+    double threshold, bool want_ice) {
+    const char* op = "partial_dependence";
+    TORCH_CHECK(X.is_cuda() && X.dtype() == at::kDouble && X.dim() == 2 &&
+                X.size(1) == FPAD && X.is_contiguous(), op,
+                ": X must be device float64 [M, 16]");
+    TORCH_CHECK(F >= 1 && F <= FPAD);
+    const long M = X.size(0);
+    auto dev = X.device();
+    TORCH_CHECK(std::isfinite(threshold) || threshold < 0.0, op,
+                ": threshold must be finite (negative: argmax rule)");
+    TORCH_CHECK(!seg_off.is_cuda() && seg_off.dtype() == at::kInt &&
+                seg_off.dim() == 1 && seg_off.numel() >= 2, op,
+                ": seg_off must be CPU int32 [G+1]");
+    const long G = seg_off.numel() - 1;
+    grouped_params_check(mean, scale, pca_mean, W, cuts, cut_off, 1, op);
+
+    TORCH_CHECK(!job_col.is_cuda() && job_col.dtype() == at::kInt &&
+                job_col.dim() == 1 && job_col.is_contiguous(), op,
+                ": job_col must be CPU int32 [J]");
+    const long J = job_col.numel();
+    TORCH_CHECK(J >= 1 && J <= DEPENDENCE_MAX_JOBS, op, ": between 1 and ",
+                DEPENDENCE_MAX_JOBS, " jobs");
+    TORCH_CHECK(!job_val.is_cuda() && job_val.dtype() == at::kDouble &&
+                job_val.dim() == 1 && job_val.is_contiguous() &&
+                job_val.numel() == J, op,
+                ": job_val must be CPU float64 [J]");
+    for (long j = 0; j < J; ++j) {
+        const int c = job_col.data_ptr<int>()[j];
+        TORCH_CHECK(c >= 0 && c < F, op, ": job ", j, " names column ", c,
+                    " of ", F);
+        TORCH_CHECK(std::isfinite(job_val.data_ptr<double>()[j]), op,
+                    ": job ", j, " has a non-finite value");
+    }
+    TORCH_CHECK(!want_ice || M * J < (1L << 31), op,
+                ": too many rows x jobs for the ICE output");
+
+    // one detector: every group's blocks read parameter set 0
+    const std::vector<int> det((size_t)G, 0);
+    auto tab_enc = holdout_block_table(seg_off, M, DETECT_BLK, dev, op,
+                                       det.data(), true);
+    static_assert(DEPENDENCE_ROWS == HOLDOUT_PROBA_ROWS,
+                  "one 64-row table serves both kernels");
+    auto tab = holdout_block_table(seg_off, M, DEPENDENCE_ROWS, dev, op,
+                                   det.data(), true);
+    // first 64-row block of every group, in the table's order
+    auto grp_blk = at::empty({G + 1}, at::kInt);
+    {
+        const int* so = seg_off.data_ptr<int>();
+        int* gb = grp_blk.data_ptr<int>();
+        gb[0] = 0;
+        for (long g = 0; g < G; ++g)
+            gb[g + 1] = gb[g] + (so[g + 1] - so[g] + DEPENDENCE_ROWS - 1)
+                                    / DEPENDENCE_ROWS;
+        TORCH_CHECK(gb[G] == tab.size(0));
+    }
+
+    TORCH_CHECK(tree_off.is_cuda() && tree_off.dtype() == at::kLong &&
+                tree_off.is_contiguous() && n_trees >= 1 &&
+                n_trees < (1L << 20) && tree_off.numel() == n_trees + 1, op,
+                ": n_trees root ids and an end");
+    TORCH_CHECK(nodes_packed.is_cuda() && nodes_packed.dtype() == at::kInt &&
+                nodes_packed.dim() == 2 && nodes_packed.size(1) == 2 &&
+                nodes_packed.is_contiguous() &&
+                nodes_packed.size(0) < (1L << 31));
+    TORCH_CHECK(tree_off.device() == dev && nodes_packed.device() == dev, op,
+                ": X and the forest must share a device");
+
+    const at::cuda::OptionalCUDAGuard guard(dev);
+    if (M == 0)
+        return {at::zeros({J + 1, G + 1}, X.options()),
+                at::zeros({J + 1, G + 1}, X.options().dtype(at::kInt)),
+                at::empty({want_ice ? J : 0, 0}, X.options())};
+    const long nb = tab.size(0);
+    // every cell of the outputs and of the per-block intermediates has
+    // exactly one writer: nothing is cleared
+    auto S = at::empty({J + 1, G + 1}, X.options());
+    auto flagged = at::empty({J + 1, G + 1}, X.options().dtype(at::kInt));
+    auto ice = want_ice ? at::empty({J, M}, X.options())
+                        : at::empty({0, 0}, X.options());
+    auto blk_sum = at::empty({J + 1, nb}, X.options());
+    auto blk_cnt = at::empty({J + 1, nb}, X.options().dtype(at::kInt));
+
+    auto mean_d = mean.to(dev), scale_d = scale.to(dev);
+    auto pmean_d = pca_mean.to(dev), W_d = W.to(dev);
+    auto cuts_d = cuts.to(dev), off_d = cut_off.to(dev);
+    auto base_d = at::zeros({1}, at::kInt).to(dev);
+    auto col_d = job_col.to(dev), val_d = job_val.to(dev);
+    auto grp_d = grp_blk.to(dev);
+    const float* cuts_p = cuts.numel() ? cuts_d.data_ptr<float>() : nullptr;
+    const int n_blocks =
+        ((int)n_trees + PREDICT_TREE_BLOCK - 1) / PREDICT_TREE_BLOCK;
+    hipStream_t s = current_stream();
+
+    // the unmodified rows, once: codes and (acc0, acc1) per row
+    auto codes = at::empty({M, FPAD}, X.options().dtype(at::kByte));
+    auto acc = at::empty({M, 2}, X.options());
+    holdout_encode_kernel<<<(int)tab_enc.size(0), DETECT_BLK, 0, s>>>(
+        X.data_ptr<double>(), (const int4*)tab_enc.data_ptr<int>(),
+        mean_d.data_ptr<double>(), scale_d.data_ptr<double>(),
+        pmean_d.data_ptr<double>(), W_d.data_ptr<double>(), has_pca ? 1 : 0,
+        cuts_p, off_d.data_ptr<int>(), base_d.data_ptr<int>(), (int)F,
+        codes.data_ptr<uint8_t>());
+    holdout_proba_kernel<<<(int)nb, DETECT_BLK, 0, s>>>(
+        codes.data_ptr<uint8_t>(), (const int4*)tab.data_ptr<int>(),
+        tree_off.data_ptr<long>(), (const int2*)nodes_packed.data_ptr<int>(),
+        (int)n_trees, n_blocks, (double2*)acc.data_ptr<double>());
+
+    // a wave per job: the job list is split over blockIdx.y as in
+    // permuted_counts (about 1024 blocks, never more shares than rounds of
+    // DEPENDENCE_WAVES jobs)
+    const long rounds = (J + DEPENDENCE_WAVES - 1) / DEPENDENCE_WAVES;
+    const long want = (1024 + nb - 1) / nb;
+    const dim3 grid((unsigned)nb,
+                    (unsigned)std::max(1L, std::min({rounds, want, 65535L})));
+    auto launch = has_pca ? partial_dependence_kernel<true>
+                          : partial_dependence_kernel<false>;
+    launch<<<grid, DETECT_BLK, 0, s>>>(
+        X.data_ptr<double>(), (const int4*)tab.data_ptr<int>(),
+        codes.data_ptr<uint8_t>(), (const double2*)acc.data_ptr<double>(),
+        col_d.data_ptr<int>(), val_d.data_ptr<double>(),
+        mean_d.data_ptr<double>(), scale_d.data_ptr<double>(),
+        pmean_d.data_ptr<double>(), W_d.data_ptr<double>(), cuts_p,
+        off_d.data_ptr<int>(), (int)F, tree_off.data_ptr<long>(),
+        (const int2*)nodes_packed.data_ptr<int>(), (int)n_trees, n_blocks,
+        (int)J, (int)M, threshold, blk_sum.data_ptr<double>(),
+        blk_cnt.data_ptr<int>(),
+        want_ice ? ice.data_ptr<double>() : nullptr);
+    dependence_reduce_kernel<<<(int)(J + 1), DEPENDENCE_REDUCE_BLK, 0, s>>>(
+        blk_sum.data_ptr<double>(), blk_cnt.data_ptr<int>(),
+        grp_d.data_ptr<int>(), (int)nb, (int)G, S.data_ptr<double>(),
+        flagged.data_ptr<int>());
+    return {S, flagged, ice};
+}
+
+// ---------------------------------------------------------------------------
 // forest proximity (similar.hip)
 // ---------------------------------------------------------------------------
 // Tree-local canonical leaf ids as int32 [M, T].  The caller guarantees a
@@ -1470,6 +1624,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("permuted_counts", &permuted_counts,
           py::call_guard<py::gil_scoped_release>(),
           "Per-group [FP, FN, TP] of J column masks x R row permutations");
+    m.def("partial_dependence", &partial_dependence,
+          py::call_guard<py::gil_scoped_release>(),
+          "fused partial-dependence / ICE jobs -> (S [J+1, G+1], flagged "
+          "[J+1, G+1], ice [J, M] or empty)");
     m.def("forest_leaves", &forest_leaves,
           py::call_guard<py::gil_scoped_release>(),
           "Per-row, per-tree canonical leaf ids over a packed forest");

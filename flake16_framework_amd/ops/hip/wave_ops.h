@@ -8,7 +8,8 @@
 //
 // EVERY primitive assumes a FULLY ACTIVE 64-lane wave (EXEC all ones):
 // DPP reads of inactive lanes are undefined.  All call sites are
-// wave-uniform code of the forest kernels (forest.hip).
+// wave-uniform code of the forest kernels (forest.hip) and of the
+// partial-dependence kernel (dependence.hip).
 //
 // Reduction shape (wave_reduce): row_shr:1,2,4,8 leave each 16-lane row's
 // reduction in its lane 15; row_bcast:15 folds row 0 into row 1 and row 2
@@ -65,6 +66,41 @@ __device__ __forceinline__ int wave_min_i32(int v) {
 }
 __device__ __forceinline__ int wave_max_i32(int v) {
     return wave_reduce(v, [](int a, int b) { return a > b ? a : b; });
+}
+
+// fp64 sum of one value per lane with a PINNED association, wave-uniform.
+// The double travels as two 32-bit DPP moves (as in wave_argmax_step).
+//
+// The result is bit for bit the pairwise tree
+//     v = v[0::2] + v[1::2]      six times over v[0..63], result v[0]
+// that numpy evaluates (engine/dependence.py).  Follow lane 63's
+// dependency chain, writing T_k[i] for the sum over lanes i-2^k+1 .. i:
+//   row_shr:1    lane 2i+1  = own v[2i+1] + lower v[2i]        tree level 1
+//   row_shr:2    lane 4i+3  = own T_1[4i+3] + lower T_1[4i+1]  level 2
+//   row_shr:4    lane 8i+7  = own T_2[8i+7] + lower T_2[8i+3]  level 3
+//   row_shr:8    lane 16i+15 = own T_3 + lower T_3[16i+7]      level 4
+//   row_bcast:15 lanes 31, 63 = own T_4 + lane 15 / 47's T_4   level 5
+//   row_bcast:31 lane 63 = own T_5[63] + lane 31's T_5         level 6
+// so every add on the chain joins the two adjacent aligned halves of a
+// tree node, upper half as the first operand: `own + lower`, where numpy
+// adds `lower + upper`.  IEEE fp64 addition of non-NaN values is
+// commutative, so the two have the same bits.  Lanes off the chain (those
+// without a DPP source add their own value, old = v) are never read.
+template <int CTRL>
+__device__ __forceinline__ double wave_dpp_f64(double v) {
+    return __hiloint2double(wave_dpp_i32<CTRL>(__double2hiint(v)),
+                            wave_dpp_i32<CTRL>(__double2loint(v)));
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {
+    v = v + wave_dpp_f64<WAVE_DPP_ROW_SHR1>(v);
+    v = v + wave_dpp_f64<WAVE_DPP_ROW_SHR2>(v);
+    v = v + wave_dpp_f64<WAVE_DPP_ROW_SHR4>(v);
+    v = v + wave_dpp_f64<WAVE_DPP_ROW_SHR8>(v);
+    v = v + wave_dpp_f64<WAVE_DPP_ROW_BCAST15>(v);
+    v = v + wave_dpp_f64<WAVE_DPP_ROW_BCAST31>(v);
+    return __hiloint2double(
+        __builtin_amdgcn_readlane(__double2hiint(v), 63),
+        __builtin_amdgcn_readlane(__double2loint(v), 63));
 }
 
 // Inclusive prefix sum over the 64 lanes (lane i gets v_0 + ... + v_i).

@@ -32,6 +32,7 @@ setup(
                      "flake16_framework_amd/ops/hip/interact.hip",
                      "flake16_framework_amd/ops/hip/holdout.hip",
                      "flake16_framework_amd/ops/hip/importance.hip",
+                     "flake16_framework_amd/ops/hip/dependence.hip",
                      "flake16_framework_amd/ops/hip/similar.hip",
                      "flake16_framework_amd/ops/hip/philox.h",
                      "flake16_framework_amd/ops/hip/wave_ops.h"],
