@@ -321,7 +321,7 @@ def fit_detector(config_keys, tests=None, tests_file=None, seed=0,
 
 
 def pack_nodes(detector):
-    """int32 [n_nodes, 2] inference records (layout: ops/hip/detect.hip).
+    """int32 [n_nodes, 2] inference records (layout: ops/hip/detector_steps.h).
     Child ids become global so a walk needs only the tree's root id."""
     d = detector
     sizes = np.diff(d.tree_off)

@@ -22,8 +22,7 @@
 // holdout_encode_kernel and holdout_proba_kernel; the first kernel reads
 // their codes and (acc0, acc1) per row, keeps them in registers across its
 // jobs and reports the baseline from them as row J (blockIdx.y == 0,
-// wave 0).  Parameters and cuts are staged into LDS once per block, as in
-// detect_encode_kernel.
+// wave 0).  Parameters and cuts are staged into LDS once per block.
 //
 // The replaced value is wave-uniform.  Without a projection its z and its
 // code are wave-uniform too, only one code byte changes, and a row whose
@@ -33,8 +32,8 @@
 // centred values are kept in LDS and the uniform term takes column f's
 // place in the sum.
 //
-// Bit-parity contract: that of detect.hip for (acc0, acc1), and for the
-// sums the reduction tree pinned in engine/dependence.py:
+// Bit-parity contract: that of detector_steps.h for (acc0, acc1) and the
+// rule, and for the sums the reduction tree pinned in engine/dependence.py:
 //   - a block is 64 consecutive rows of a project from its first row; its
 //     sum B is the pairwise tree v = v[0::2] + v[1::2] six times over the
 //     rows' acc1, 0.0 past the last row: wave_sum_f64 (wave_ops.h) is that
@@ -50,8 +49,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "detect.hip"
-#include "importance.hip"
+#include "detector_steps.h"
 #include "wave_ops.h"
 
 #pragma clang fp contract(off)
@@ -83,35 +81,23 @@ __global__ __launch_bounds__(DETECT_BLK) void partial_dependence_kernel(
     double* __restrict__ blk_sum,          // [J + 1, gridDim.x]
     int* __restrict__ blk_cnt,             // [J + 1, gridDim.x]
     double* __restrict__ ice /* [J, M] acc1, or null */) {
-    __shared__ double s_mean[FPAD], s_scale[FPAD], s_pmean[FPAD];
-    __shared__ double s_W[FPAD * FPAD];
-    __shared__ float s_cuts[FPAD * DETECT_MAX_CUTS];
-    __shared__ int s_off[FPAD + 1];
+    // s_own is placed on a 16-byte boundary: 8 B of padding follow the
+    // 18,824 B of s
+    __shared__ DetectorLds s;
     __shared__ double s_own[HAS_PCA ? FPAD * DEPENDENCE_ROWS : 1];
 
     const int tid = threadIdx.x;
     const int lane = tid % DEPENDENCE_ROWS;
     const int wave = __builtin_amdgcn_readfirstlane(tid / DEPENDENCE_ROWS);
     const int4 blk = blk_tab[blockIdx.x];
-    if (tid < FPAD) {
-        s_mean[tid] = mean[tid];
-        s_scale[tid] = scale[tid];
-        s_pmean[tid] = pca_mean[tid];
-    }
-    if (tid <= FPAD) s_off[tid] = cut_off[tid];
-    s_W[tid] = W[tid];                     // DETECT_BLK == FPAD * FPAD
-    const int n_cuts = cut_off[FPAD];
-    for (int i = tid; i < n_cuts; i += DETECT_BLK) s_cuts[i] = cuts[i];
-    __syncthreads();
+    stage_detector(s, mean, scale, pca_mean, W, cuts, cut_off);
 
     // lanes past the block's last row repeat it and are masked out of
     // every result, so every lane reads valid rows and the wave is fully
     // active where it reduces
     const bool live = blk.y + lane < blk.z;
     const int row = live ? blk.y + lane : blk.z - 1;
-    const uint4 cw = *(const uint4*)(base_codes + (size_t)row * FPAD);
-    const uint64_t b_lo = (uint64_t)cw.x | ((uint64_t)cw.y << 32);
-    const uint64_t b_hi = (uint64_t)cw.z | ((uint64_t)cw.w << 32);
+    const RowCodes b_codes = load_codes(base_codes, row);
     const double2 b_acc = base_acc[row];
 
     // the rows' own centred values z[f] - pca_mean[f], column-major (the
@@ -120,16 +106,13 @@ __global__ __launch_bounds__(DETECT_BLK) void partial_dependence_kernel(
         for (int f = wave * (FPAD / DEPENDENCE_WAVES);
              f < (wave + 1) * (FPAD / DEPENDENCE_WAVES); ++f)
             s_own[f * DEPENDENCE_ROWS + lane] =
-                (X[(size_t)row * FPAD + f] - s_mean[f]) / s_scale[f]
-                - s_pmean[f];
+                scaled(s, f, X[(size_t)row * FPAD + f]) - s.pmean[f];
         __syncthreads();
     }
 
     const size_t nb = gridDim.x;
     if (blockIdx.y == 0 && wave == 0) {
-        const bool pred = threshold < 0.0
-            ? b_acc.y > b_acc.x
-            : b_acc.y / (double)n_trees >= threshold;
+        const bool pred = predicted(b_acc, n_trees, threshold);
         const int cnt = __popcll(__ballot(live && pred));
         const double B = wave_sum_f64(live ? b_acc.y : 0.0);
         if (lane == 0) {
@@ -142,11 +125,11 @@ __global__ __launch_bounds__(DETECT_BLK) void partial_dependence_kernel(
          job += gridDim.y * DEPENDENCE_WAVES) {
         // wave-uniform: the job's column and its scaled value
         const int jf = job_col[job];
-        const double jz = (job_val[job] - s_mean[jf]) / s_scale[jf];
+        const double jz = scaled(s, jf, job_val[job]);
 
-        uint64_t c_lo, c_hi;
+        RowCodes c;
         if (HAS_PCA) {
-            const double jd = jz - s_pmean[jf];
+            const double jd = jz - s.pmean[jf];
             double t[FPAD];
 #pragma unroll
             for (int k = 0; k < FPAD; ++k) t[k] = 0.0;
@@ -158,66 +141,25 @@ __global__ __launch_bounds__(DETECT_BLK) void partial_dependence_kernel(
                     f == jf ? jd : s_own[f * DEPENDENCE_ROWS + lane];
 #pragma unroll
                 for (int k = 0; k < FPAD; ++k)
-                    t[k] = t[k] + dv * s_W[f * FPAD + k];
+                    t[k] = t[k] + dv * s.W[f * FPAD + k];
             }
-            c_lo = c_hi = 0;
-#pragma unroll
-            for (int f = 0; f < FPAD; ++f) {
-                if (f < F) {
-                    const uint64_t code =
-                        importance_code(s_cuts, s_off, f, t[f]);
-                    if (f < 8) c_lo |= code << (f * 8);
-                    else c_hi |= code << ((f - 8) * 8);
-                }
-            }
+            c = search_codes(s, t, F);
         } else {
-            const uint64_t code = __builtin_amdgcn_readfirstlane(
-                importance_code(s_cuts, s_off, jf, jz));
-            const int sh = (jf & 7) * 8;
-            const uint64_t keep = ~(0xFFull << sh);
-            c_lo = jf & 8 ? b_lo : (b_lo & keep) | code << sh;
-            c_hi = jf & 8 ? (b_hi & keep) | code << sh : b_hi;
+            c = with_code(b_codes, jf, __builtin_amdgcn_readfirstlane(
+                                           cut_code(s, jf, jz)));
         }
 
-        double tot0 = b_acc.x, tot1 = b_acc.y;
-        if (c_lo != b_lo || c_hi != b_hi) {
-            tot0 = 0.0;
-            tot1 = 0.0;
-            for (int tb = 0; tb < n_blocks; ++tb) {
-                const int t0 = tb * PREDICT_TREE_BLOCK;
-                const int t1 = min(n_trees, t0 + PREDICT_TREE_BLOCK);
-                double acc0 = 0.0, acc1 = 0.0;
-                for (int t = t0; t < t1; ++t) {
-                    int2 nd = nodes[tree_off[t]];
-                    while (nd.x < 0) {
-                        const int f = nd.y & 0xFF;
-                        const int code = (int)(
-                            ((f & 8 ? c_hi : c_lo) >> ((f & 7) * 8)) & 0xFF);
-                        nd = nodes[(nd.x & 0x7FFFFFFF)
-                                   + (code > (nd.y >> 8))];
-                    }
-                    const double c0 = (double)__int_as_float(nd.x);
-                    const double c1 = (double)__int_as_float(nd.y);
-                    const double tot = c0 + c1;
-                    acc0 += c0 / tot;
-                    acc1 += c1 / tot;
-                }
-                tot0 += acc0;
-                tot1 += acc1;
-            }
-        }
-
-        // the walk above diverges per lane; the wave is whole again here
-        const bool pred = threshold < 0.0
-            ? tot1 > tot0
-            : tot1 / (double)n_trees >= threshold;
+        // the walk diverges per lane; the wave is whole again after it
+        const double2 acc = same_codes(c, b_codes)
+            ? b_acc : forest_sums(nodes, tree_off, n_trees, n_blocks, c);
+        const bool pred = predicted(acc, n_trees, threshold);
         const int cnt = __popcll(__ballot(live && pred));
-        const double B = wave_sum_f64(live ? tot1 : 0.0);
+        const double B = wave_sum_f64(live ? acc.y : 0.0);
         if (lane == 0) {
             blk_sum[(size_t)job * nb + blockIdx.x] = B;
             blk_cnt[(size_t)job * nb + blockIdx.x] = cnt;
         }
-        if (ice != nullptr && live) ice[(size_t)job * M + row] = tot1;
+        if (ice != nullptr && live) ice[(size_t)job * M + row] = acc.y;
     }
 }
 

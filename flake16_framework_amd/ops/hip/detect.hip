@@ -7,44 +7,20 @@
 //                          per-row (acc0, acc1) class-probability sums
 //                          over a packed inference forest
 //
-// Bit-parity contract (host side: preprocess.transform_preprocessing,
-// models/binning.bin_codes, models/forest_ref.accumulate_proba):
-//   - z[f] = (x[f] - mean[f]) / scale[f]                       (fp64)
-//   - t[k] = sum over ascending f of (z[f] - pca_mean[f]) * W[f][k],
-//     from 0.0, separate multiply and add — contraction must stay off
-//     (the build passes -ffp-contract=off; the pragma below pins it for
-//     this file whatever the command line says)
-//   - code = #{cut <= (float)value}
-//   - tree probabilities summed sequentially within blocks of
-//     PREDICT_TREE_BLOCK trees, blocks added in ascending order.
-//
-// Packed node (8 bytes, one load per tree level):
-//   internal  x = 0x80000000 | id of the left child (global, into the
-//                 packed array; the right child is the next record)
-//             y = split_bin << 8 | feature
-//   leaf      x, y = bit patterns of the fp32 class counts cnt0, cnt1
-// Counts are non-negative, so the sign bit of x tells the kinds apart.
+// The steps, the packed node format and the bit-parity contract are in
+// detector_steps.h.
 
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "detector_steps.h"
+
 #pragma clang fp contract(off)
 
-#ifndef FPAD
-#define FPAD 16
-#endif
-#ifndef PREDICT_TREE_BLOCK
-#define PREDICT_TREE_BLOCK 10
-#endif
-
-#define DETECT_BLK 256
-#define DETECT_MAX_CUTS 255   // per feature: codes are uint8
-
 // One thread per row.  Parameters and cuts are staged into LDS once per
-// block (2432 B of doubles + <= 16320 B of cuts + the offset table); the
-// projection reads them wave-uniformly (LDS broadcast).
+// block.
 __global__ __launch_bounds__(DETECT_BLK) void detect_encode_kernel(
     const double* __restrict__ X,          // [M, FPAD] raw, zero-padded
     const double* __restrict__ mean,       // [FPAD]
@@ -52,71 +28,17 @@ __global__ __launch_bounds__(DETECT_BLK) void detect_encode_kernel(
     const double* __restrict__ pca_mean,   // [FPAD]
     const double* __restrict__ W,          // [FPAD, FPAD], W[f][k]
     int has_pca,
-    const float* __restrict__ cuts,        // flat, n_cuts entries
+    const float* __restrict__ cuts,        // flat, cut_off[FPAD] entries
     const int* __restrict__ cut_off,       // [FPAD + 1]
-    int n_cuts, int M, int F,
+    int M, int F,
     uint8_t* __restrict__ codes /* [M, FPAD] */) {
-    __shared__ double s_mean[FPAD], s_scale[FPAD], s_pmean[FPAD];
-    __shared__ double s_W[FPAD * FPAD];
-    __shared__ float s_cuts[FPAD * DETECT_MAX_CUTS];
-    __shared__ int s_off[FPAD + 1];
+    __shared__ DetectorLds s;
+    stage_detector(s, mean, scale, pca_mean, W, cuts, cut_off);
 
-    const int tid = threadIdx.x;
-    if (tid < FPAD) {
-        s_mean[tid] = mean[tid];
-        s_scale[tid] = scale[tid];
-        s_pmean[tid] = pca_mean[tid];
-    }
-    if (tid <= FPAD) s_off[tid] = cut_off[tid];
-    s_W[tid] = W[tid];                     // DETECT_BLK == FPAD * FPAD
-    for (int i = tid; i < n_cuts; i += DETECT_BLK) s_cuts[i] = cuts[i];
-    __syncthreads();
-
-    const long row = (long)blockIdx.x * DETECT_BLK + tid;
+    const long row = (long)blockIdx.x * DETECT_BLK + threadIdx.x;
     if (row >= M) return;
-
-    double v[FPAD];
-    const double2* xr = (const double2*)(X + (size_t)row * FPAD);
-#pragma unroll
-    for (int f = 0; f < FPAD; f += 2) {
-        const double2 x2 = xr[f >> 1];
-        v[f] = (x2.x - s_mean[f]) / s_scale[f];
-        v[f + 1] = (x2.y - s_mean[f + 1]) / s_scale[f + 1];
-    }
-
-    if (has_pca) {
-        double t[FPAD];
-#pragma unroll
-        for (int k = 0; k < FPAD; ++k) t[k] = 0.0;
-#pragma unroll
-        for (int f = 0; f < FPAD; ++f) {
-            if (f < F) {
-                const double d = v[f] - s_pmean[f];
-#pragma unroll
-                for (int k = 0; k < FPAD; ++k)
-                    t[k] = t[k] + d * s_W[f * FPAD + k];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < FPAD; ++k) v[k] = t[k];
-    }
-
-    uint32_t out[FPAD / 4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int f = 0; f < FPAD; ++f) {
-        if (f < F) {
-            const float x = (float)v[f];
-            const float* c = s_cuts + s_off[f];
-            int lo = 0, hi = s_off[f + 1] - s_off[f];
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (c[mid] <= x) lo = mid + 1; else hi = mid;
-            }
-            out[f >> 2] |= (uint32_t)lo << ((f & 3) * 8);
-        }
-    }
-    *(uint4*)(codes + (size_t)row * FPAD) =
-        make_uint4(out[0], out[1], out[2], out[3]);
+    store_codes(codes, row,
+                encode_row(s, X + (size_t)row * FPAD, has_pca, F));
 }
 
 // Stage 1: one thread per (row, block of PREDICT_TREE_BLOCK trees), rows
@@ -133,29 +55,8 @@ __global__ __launch_bounds__(DETECT_BLK) void forest_proba_partial_kernel(
     if (idx >= (long)M * n_blocks) return;
     const int row = (int)(idx % M);
     const int tb = (int)(idx / M);
-
-    const uint4 cw = *(const uint4*)(codes + (size_t)row * FPAD);
-    const uint64_t c_lo = (uint64_t)cw.x | ((uint64_t)cw.y << 32);
-    const uint64_t c_hi = (uint64_t)cw.z | ((uint64_t)cw.w << 32);
-
-    const int t0 = tb * PREDICT_TREE_BLOCK;
-    const int t1 = min(n_trees, t0 + PREDICT_TREE_BLOCK);
-    double acc0 = 0.0, acc1 = 0.0;
-    for (int t = t0; t < t1; ++t) {
-        int2 nd = nodes[tree_off[t]];
-        while (nd.x < 0) {
-            const int f = nd.y & 0xFF;
-            const int code =
-                (int)(((f & 8 ? c_hi : c_lo) >> ((f & 7) * 8)) & 0xFF);
-            nd = nodes[(nd.x & 0x7FFFFFFF) + (code > (nd.y >> 8))];
-        }
-        const double c0 = (double)__int_as_float(nd.x);
-        const double c1 = (double)__int_as_float(nd.y);
-        const double tot = c0 + c1;
-        acc0 += c0 / tot;
-        acc1 += c1 / tot;
-    }
-    partial[(size_t)tb * M + row] = make_double2(acc0, acc1);
+    partial[(size_t)tb * M + row] = tree_block_sums(
+        nodes, tree_off, tb, n_trees, load_codes(codes, row));
 }
 
 // Stage 2: one thread per row, tree blocks added in ascending order.

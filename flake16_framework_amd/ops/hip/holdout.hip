@@ -8,8 +8,8 @@
 // so a block serves exactly one group, groups without rows get no block,
 // and nothing is gathered per row.
 //
-//   holdout_encode_kernel     detect_encode_kernel with the block's group
-//                             choosing parameters and cuts
+//   holdout_encode_kernel     detect_encode_kernel's body with the block's
+//                             group choosing parameters and cuts
 //   holdout_proba_kernel      forest_proba in one launch: a wave per tree
 //                             block, partial sums combined through LDS in
 //                             ascending tree-block order
@@ -17,19 +17,18 @@
 //                             argmax rule and under proba >= t_k for K
 //                             thresholds, integer atomics only
 //
-// Bit-parity contract: that of detect.hip, per group.  holdout_encode is
-// detect_encode on the group's slice; holdout_proba keeps the
-// PREDICT_TREE_BLOCK association (trees summed sequentially from 0.0
-// within a block of trees, block sums added to 0.0 in ascending order);
-// threshold_counts forms proba = acc1 / (double)n_trees, the host's single
-// division, and counts with integers, so no result depends on scheduling.
+// Bit-parity contract: that of detector_steps.h, per group.
+// holdout_encode is detect_encode on the group's slice; holdout_proba adds
+// the tree-block sums in ascending order; threshold_counts forms
+// proba = acc1 / (double)n_trees and counts with integers, so no result
+// depends on scheduling.
 
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "detect.hip"
+#include "detector_steps.h"
 
 #pragma clang fp contract(off)
 
@@ -37,10 +36,12 @@
 #define HOLDOUT_PROBA_WAVES (DETECT_BLK / HOLDOUT_PROBA_ROWS)
 #define HOLDOUT_MAX_K 256         // thresholds per call: one per thread
 
-// One thread per row, DETECT_BLK rows per block.  LDS as in
-// detect_encode_kernel: the group's parameters and cuts, staged once.
-// The waves-per-SIMD hint keeps the allocation at detect_encode_kernel's
-// 5 waves (without it the group indexing costs 6 VGPRs and one wave).
+// One thread per row, DETECT_BLK rows per block; the group's parameters
+// and cuts are staged once.  The waves-per-SIMD hint dates from the
+// kernel's own copy of the encode body, which needed it to stay at 5 waves.
+// With the shared body the kernel reaches 5 waves without it (81 VGPRs
+// against 92 with it); it is kept only because the kernel without it has
+// not been timed.
 __global__ __launch_bounds__(DETECT_BLK)
 __attribute__((amdgpu_waves_per_eu(5, 5))) void holdout_encode_kernel(
     const double* __restrict__ X,          // [M, FPAD] raw, zero-padded
@@ -55,71 +56,17 @@ __attribute__((amdgpu_waves_per_eu(5, 5))) void holdout_encode_kernel(
     const int* __restrict__ cut_base,      // [G] group's first cut
     int F,
     uint8_t* __restrict__ codes /* [M, FPAD] */) {
-    __shared__ double s_mean[FPAD], s_scale[FPAD], s_pmean[FPAD];
-    __shared__ double s_W[FPAD * FPAD];
-    __shared__ float s_cuts[FPAD * DETECT_MAX_CUTS];
-    __shared__ int s_off[FPAD + 1];
-
-    const int tid = threadIdx.x;
+    __shared__ DetectorLds s;
     const int4 blk = blk_tab[blockIdx.x];
     const int g = blk.x;
-    if (tid < FPAD) {
-        s_mean[tid] = mean[g * FPAD + tid];
-        s_scale[tid] = scale[g * FPAD + tid];
-        s_pmean[tid] = pca_mean[g * FPAD + tid];
-    }
-    if (tid <= FPAD) s_off[tid] = cut_off[g * (FPAD + 1) + tid];
-    s_W[tid] = W[(size_t)g * FPAD * FPAD + tid];   // DETECT_BLK == FPAD^2
-    const int n_cuts = cut_off[g * (FPAD + 1) + FPAD];
-    const float* gcuts = cuts + cut_base[g];
-    for (int i = tid; i < n_cuts; i += DETECT_BLK) s_cuts[i] = gcuts[i];
-    __syncthreads();
+    stage_detector(s, mean + g * FPAD, scale + g * FPAD,
+                   pca_mean + g * FPAD, W + (size_t)g * FPAD * FPAD,
+                   cuts + cut_base[g], cut_off + g * (FPAD + 1));
 
-    const int row = blk.y + tid;
+    const int row = blk.y + threadIdx.x;
     if (row >= blk.z) return;
-
-    double v[FPAD];
-    const double2* xr = (const double2*)(X + (size_t)row * FPAD);
-#pragma unroll
-    for (int f = 0; f < FPAD; f += 2) {
-        const double2 x2 = xr[f >> 1];
-        v[f] = (x2.x - s_mean[f]) / s_scale[f];
-        v[f + 1] = (x2.y - s_mean[f + 1]) / s_scale[f + 1];
-    }
-
-    if (has_pca) {
-        double t[FPAD];
-#pragma unroll
-        for (int k = 0; k < FPAD; ++k) t[k] = 0.0;
-#pragma unroll
-        for (int f = 0; f < FPAD; ++f) {
-            if (f < F) {
-                const double d = v[f] - s_pmean[f];
-#pragma unroll
-                for (int k = 0; k < FPAD; ++k)
-                    t[k] = t[k] + d * s_W[f * FPAD + k];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < FPAD; ++k) v[k] = t[k];
-    }
-
-    uint32_t out[FPAD / 4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int f = 0; f < FPAD; ++f) {
-        if (f < F) {
-            const float x = (float)v[f];
-            const float* c = s_cuts + s_off[f];
-            int lo = 0, hi = s_off[f + 1] - s_off[f];
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (c[mid] <= x) lo = mid + 1; else hi = mid;
-            }
-            out[f >> 2] |= (uint32_t)lo << ((f & 3) * 8);
-        }
-    }
-    *(uint4*)(codes + (size_t)row * FPAD) =
-        make_uint4(out[0], out[1], out[2], out[3]);
+    store_codes(codes, row,
+                encode_row(s, X + (size_t)row * FPAD, has_pca, F));
 }
 
 // HOLDOUT_PROBA_ROWS rows per block, one per lane; wave w walks tree
@@ -143,36 +90,16 @@ __global__ __launch_bounds__(DETECT_BLK) void holdout_proba_kernel(
     const int row = blk.y + lane;
     const bool live = row < blk.z;
 
-    uint64_t c_lo = 0, c_hi = 0;
-    if (live) {
-        const uint4 cw = *(const uint4*)(codes + (size_t)row * FPAD);
-        c_lo = (uint64_t)cw.x | ((uint64_t)cw.y << 32);
-        c_hi = (uint64_t)cw.z | ((uint64_t)cw.w << 32);
-    }
+    RowCodes c = {0, 0};
+    if (live) c = load_codes(codes, row);
 
     double tot0 = 0.0, tot1 = 0.0;
     for (int tb0 = 0; tb0 < n_blocks; tb0 += HOLDOUT_PROBA_WAVES) {
         const int tb = tb0 + wave;
-        double acc0 = 0.0, acc1 = 0.0;
-        if (live && tb < n_blocks) {
-            const int t0 = tb * PREDICT_TREE_BLOCK;
-            const int t1 = min(n_trees, t0 + PREDICT_TREE_BLOCK);
-            for (int t = t0; t < t1; ++t) {
-                int2 nd = nodes[roots[t]];
-                while (nd.x < 0) {
-                    const int f = nd.y & 0xFF;
-                    const int code = (int)(
-                        ((f & 8 ? c_hi : c_lo) >> ((f & 7) * 8)) & 0xFF);
-                    nd = nodes[(nd.x & 0x7FFFFFFF) + (code > (nd.y >> 8))];
-                }
-                const double c0 = (double)__int_as_float(nd.x);
-                const double c1 = (double)__int_as_float(nd.y);
-                const double tot = c0 + c1;
-                acc0 += c0 / tot;
-                acc1 += c1 / tot;
-            }
-        }
-        s_part[wave][lane] = make_double2(acc0, acc1);
+        double2 part = make_double2(0.0, 0.0);
+        if (live && tb < n_blocks)
+            part = tree_block_sums(nodes, roots, tb, n_trees, c);
+        s_part[wave][lane] = part;
         __syncthreads();
         if (wave == 0) {
             const int nw = min(HOLDOUT_PROBA_WAVES, n_blocks - tb0);

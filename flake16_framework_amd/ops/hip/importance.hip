@@ -17,16 +17,10 @@
 // holdout_encode_kernel and holdout_proba_kernel; this kernel reads their
 // codes and (acc0, acc1) per row, keeps them in registers across its jobs
 // and counts the baseline from them (blockIdx.y == 0, wave 0).  The
-// block's parameters and cuts are staged into LDS once, as in
-// detect_encode_kernel.
+// block's parameters and cuts are staged into LDS once.
 //
-// Bit-parity contract: that of detect.hip and holdout.hip.
-//   - z = (x - mean) / scale; the projection is summed from 0.0 over
-//     ascending f with separate multiply and add (contraction off)
-//   - code = #{cut <= (float)value}
-//   - per-tree c / (c0 + c1) summed sequentially from 0.0 inside blocks of
-//     PREDICT_TREE_BLOCK trees, block sums added to 0.0 in ascending order
-//   - proba = acc1 / (double)n_trees; argmax is acc1 > acc0 (ties 0)
+// Bit-parity contract: that of detector_steps.h for codes, sums and the
+// rule, and
 //   - counts are integers: a wave holds all of its block's rows for a job,
 //     so a cell's block total is a popcount of a ballot, added with one
 //     integer atomic per non-zero cell to the group's row and to the pooled
@@ -43,25 +37,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "detect.hip"
+#include "detector_steps.h"
 
 #pragma clang fp contract(off)
 
 #define IMPORTANCE_ROWS 64        // rows per block: one per lane
 #define IMPORTANCE_WAVES (DETECT_BLK / IMPORTANCE_ROWS)
-
-__device__ __forceinline__ uint32_t importance_code(
-    const float* __restrict__ s_cuts, const int* __restrict__ s_off, int f,
-    double value) {
-    const float x = (float)value;
-    const float* c = s_cuts + s_off[f];
-    int lo = 0, hi = s_off[f + 1] - s_off[f];
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (c[mid] <= x) lo = mid + 1; else hi = mid;
-    }
-    return (uint32_t)lo;
-}
 
 template <bool HAS_PCA>
 __global__ __launch_bounds__(DETECT_BLK) void permuted_counts_kernel(
@@ -86,10 +67,9 @@ __global__ __launch_bounds__(DETECT_BLK) void permuted_counts_kernel(
     double threshold,                      // < 0: argmax rule
     int* __restrict__ counts,              // [J, R, G + 1, 3] zeroed
     int* __restrict__ baseline /* [G + 1, 3] zeroed */) {
-    __shared__ double s_mean[FPAD], s_scale[FPAD], s_pmean[FPAD];
-    __shared__ double s_W[FPAD * FPAD];
-    __shared__ float s_cuts[FPAD * DETECT_MAX_CUTS];
-    __shared__ int s_off[FPAD + 1];
+    // s_own is placed on a 16-byte boundary: 8 B of padding follow the
+    // 18,824 B of s
+    __shared__ DetectorLds s;
     __shared__ double s_own[HAS_PCA ? FPAD * IMPORTANCE_ROWS : 1];
 
     const int tid = threadIdx.x;
@@ -97,17 +77,9 @@ __global__ __launch_bounds__(DETECT_BLK) void permuted_counts_kernel(
     const int wave = __builtin_amdgcn_readfirstlane(tid / IMPORTANCE_ROWS);
     const int4 blk = blk_tab[blockIdx.x];
     const int g = blk.x, d = blk.w;
-    if (tid < FPAD) {
-        s_mean[tid] = mean[d * FPAD + tid];
-        s_scale[tid] = scale[d * FPAD + tid];
-        s_pmean[tid] = pca_mean[d * FPAD + tid];
-    }
-    if (tid <= FPAD) s_off[tid] = cut_off[d * (FPAD + 1) + tid];
-    s_W[tid] = W[(size_t)d * FPAD * FPAD + tid];   // DETECT_BLK == FPAD^2
-    const int n_cuts = cut_off[d * (FPAD + 1) + FPAD];
-    const float* dcuts = cuts + cut_base[d];
-    for (int i = tid; i < n_cuts; i += DETECT_BLK) s_cuts[i] = dcuts[i];
-    __syncthreads();
+    stage_detector(s, mean + d * FPAD, scale + d * FPAD,
+                   pca_mean + d * FPAD, W + (size_t)d * FPAD * FPAD,
+                   cuts + cut_base[d], cut_off + d * (FPAD + 1));
 
     // lanes past the block's last row repeat it and are left out of the
     // counts, so every lane reads valid rows and the wave never diverges
@@ -115,9 +87,7 @@ __global__ __launch_bounds__(DETECT_BLK) void permuted_counts_kernel(
     const bool live = blk.y + lane < blk.z;
     const int row = live ? blk.y + lane : blk.z - 1;
     const int y = labels[row] != 0;
-    const uint4 cw = *(const uint4*)(base_codes + (size_t)row * FPAD);
-    const uint64_t b_lo = (uint64_t)cw.x | ((uint64_t)cw.y << 32);
-    const uint64_t b_hi = (uint64_t)cw.z | ((uint64_t)cw.w << 32);
+    const RowCodes b_codes = load_codes(base_codes, row);
     const double2 b_acc = base_acc[row];
     const long* roots = tree_off + (size_t)d * n_trees;
 
@@ -128,23 +98,20 @@ __global__ __launch_bounds__(DETECT_BLK) void permuted_counts_kernel(
         for (int f = wave * (FPAD / IMPORTANCE_WAVES);
              f < (wave + 1) * (FPAD / IMPORTANCE_WAVES); ++f)
             s_own[f * IMPORTANCE_ROWS + lane] =
-                (X[(size_t)row * FPAD + f] - s_mean[f]) / s_scale[f]
-                - s_pmean[f];
+                scaled(s, f, X[(size_t)row * FPAD + f]) - s.pmean[f];
         __syncthreads();
     }
 
     if (blockIdx.y == 0 && wave == 0) {
-        const bool pred = threshold < 0.0
-            ? b_acc.y > b_acc.x
-            : b_acc.y / (double)n_trees >= threshold;
+        const bool pred = predicted(b_acc, n_trees, threshold);
         const int fp = __popcll(__ballot(live && pred && !y));
         const int fn = __popcll(__ballot(live && !pred && y));
         const int tp = __popcll(__ballot(live && pred && y));
         if (lane < 3) {
-            const int c = lane == 0 ? fp : lane == 1 ? fn : tp;
-            if (c) {
-                atomicAdd(baseline + g * 3 + lane, c);
-                atomicAdd(baseline + G * 3 + lane, c);
+            const int n = lane == 0 ? fp : lane == 1 ? fn : tp;
+            if (n) {
+                atomicAdd(baseline + g * 3 + lane, n);
+                atomicAdd(baseline + G * 3 + lane, n);
             }
         }
     }
@@ -158,7 +125,7 @@ __global__ __launch_bounds__(DETECT_BLK) void permuted_counts_kernel(
         // f and the mask are wave-uniform: the column loops stay rolled
         // so that one column's load, division and search are live at a
         // time
-        uint64_t c_lo, c_hi;
+        RowCodes c;
         if (HAS_PCA) {
             double t[FPAD];
 #pragma unroll
@@ -167,78 +134,35 @@ __global__ __launch_bounds__(DETECT_BLK) void permuted_counts_kernel(
             for (int f = 0; f < F; ++f) {
                 double dv;
                 if (mask >> f & 1)
-                    dv = (xs[f] - s_mean[f]) / s_scale[f] - s_pmean[f];
+                    dv = scaled(s, f, xs[f]) - s.pmean[f];
                 else
                     dv = s_own[f * IMPORTANCE_ROWS + lane];
 #pragma unroll
                 for (int k = 0; k < FPAD; ++k)
-                    t[k] = t[k] + dv * s_W[f * FPAD + k];
+                    t[k] = t[k] + dv * s.W[f * FPAD + k];
             }
-            c_lo = c_hi = 0;
-#pragma unroll
-            for (int f = 0; f < FPAD; ++f) {
-                if (f < F) {
-                    const uint64_t code =
-                        importance_code(s_cuts, s_off, f, t[f]);
-                    if (f < 8) c_lo |= code << (f * 8);
-                    else c_hi |= code << ((f - 8) * 8);
-                }
-            }
+            c = search_codes(s, t, F);
         } else {
-            c_lo = b_lo;
-            c_hi = b_hi;
+            c = b_codes;
 #pragma unroll 1
             for (int m = mask; m; m &= m - 1) {
                 const int f = __builtin_ctz(m);
-                const uint64_t code = importance_code(
-                    s_cuts, s_off, f, (xs[f] - s_mean[f]) / s_scale[f]);
-                const int sh = (f & 7) * 8;
-                const uint64_t keep = ~(0xFFull << sh);
-                if (f & 8) c_hi = (c_hi & keep) | code << sh;
-                else c_lo = (c_lo & keep) | code << sh;
+                c = with_code(c, f, cut_code(s, f, scaled(s, f, xs[f])));
             }
         }
 
-        double tot0 = b_acc.x, tot1 = b_acc.y;
-        if (c_lo != b_lo || c_hi != b_hi) {
-            tot0 = 0.0;
-            tot1 = 0.0;
-            for (int tb = 0; tb < n_blocks; ++tb) {
-                const int t0 = tb * PREDICT_TREE_BLOCK;
-                const int t1 = min(n_trees, t0 + PREDICT_TREE_BLOCK);
-                double acc0 = 0.0, acc1 = 0.0;
-                for (int t = t0; t < t1; ++t) {
-                    int2 nd = nodes[roots[t]];
-                    while (nd.x < 0) {
-                        const int f = nd.y & 0xFF;
-                        const int code = (int)(
-                            ((f & 8 ? c_hi : c_lo) >> ((f & 7) * 8)) & 0xFF);
-                        nd = nodes[(nd.x & 0x7FFFFFFF)
-                                   + (code > (nd.y >> 8))];
-                    }
-                    const double c0 = (double)__int_as_float(nd.x);
-                    const double c1 = (double)__int_as_float(nd.y);
-                    const double tot = c0 + c1;
-                    acc0 += c0 / tot;
-                    acc1 += c1 / tot;
-                }
-                tot0 += acc0;
-                tot1 += acc1;
-            }
-        }
-
-        const bool pred = threshold < 0.0
-            ? tot1 > tot0
-            : tot1 / (double)n_trees >= threshold;
+        const double2 acc = same_codes(c, b_codes)
+            ? b_acc : forest_sums(nodes, roots, n_trees, n_blocks, c);
+        const bool pred = predicted(acc, n_trees, threshold);
         const int fp = __popcll(__ballot(live && pred && !y));
         const int fn = __popcll(__ballot(live && !pred && y));
         const int tp = __popcll(__ballot(live && pred && y));
         if (lane < 3) {
-            const int c = lane == 0 ? fp : lane == 1 ? fn : tp;
-            if (c) {
+            const int n = lane == 0 ? fp : lane == 1 ? fn : tp;
+            if (n) {
                 int* out = counts + (size_t)job * (G + 1) * 3;
-                atomicAdd(out + g * 3 + lane, c);
-                atomicAdd(out + G * 3 + lane, c);
+                atomicAdd(out + g * 3 + lane, n);
+                atomicAdd(out + G * 3 + lane, n);
             }
         }
     }

@@ -681,6 +681,131 @@ at::Tensor treeshap_paths(at::Tensor codes, at::Tensor leaf_tree,
 }
 
 // ---------------------------------------------------------------------------
+// checks and launch arithmetic the saved-detector ops share
+// (detector_steps.h and the kernel files built on it)
+// ---------------------------------------------------------------------------
+static void check_raw_rows(const at::Tensor& X, int64_t F, const char* op) {
+    TORCH_CHECK(X.is_cuda() && X.dtype() == at::kDouble && X.dim() == 2 &&
+                X.size(1) == FPAD && X.is_contiguous() &&
+                X.size(0) < (1L << 31), op,
+                ": X must be device float64 [M, 16]");
+    TORCH_CHECK(F >= 1 && F <= FPAD, op, ": F must be between 1 and 16");
+}
+
+static void check_codes(const at::Tensor& codes, const char* op) {
+    TORCH_CHECK(codes.is_cuda() && codes.dtype() == at::kByte &&
+                codes.dim() == 2 && codes.size(1) == FPAD &&
+                codes.is_contiguous() && codes.size(0) < (1L << 31), op,
+                ": codes must be device uint8 [M, 16]");
+}
+
+static void check_labels(const at::Tensor& labels, long M, const char* op) {
+    TORCH_CHECK(labels.is_cuda() && labels.dtype() == at::kByte &&
+                labels.dim() == 1 && labels.is_contiguous() &&
+                labels.numel() == M, op, ": labels must be device uint8 [M]");
+}
+
+// D packed forests of n_trees trees each, back to back: the
+// root ids of forest d are tree_off[d * n_trees ..], node ids are global.
+// The caller guarantees well-formed forests (engine/detector.py validates
+// child ids before packing); shapes are checked here.
+static void check_forest(const at::Tensor& tree_off,
+                         const at::Tensor& nodes_packed, long D,
+                         int64_t n_trees, long max_trees, const char* op) {
+    TORCH_CHECK(tree_off.is_cuda() && tree_off.dtype() == at::kLong &&
+                tree_off.is_contiguous() && n_trees >= 1 &&
+                n_trees <= max_trees &&
+                tree_off.numel() == D * n_trees + 1, op,
+                ": n_trees root ids per forest and an end");
+    TORCH_CHECK(nodes_packed.is_cuda() && nodes_packed.dtype() == at::kInt &&
+                nodes_packed.dim() == 2 && nodes_packed.size(1) == 2 &&
+                nodes_packed.is_contiguous() &&
+                nodes_packed.size(0) < (1L << 31), op,
+                ": nodes must be device int32 [n_nodes, 2]");
+}
+// n_trees bound of holdout_proba, permuted_counts and partial_dependence
+static const long MAX_GROUPED_TREES = (1L << 20) - 1;
+
+static int n_tree_blocks(int64_t n_trees) {
+    return ((int)n_trees + PREDICT_TREE_BLOCK - 1) / PREDICT_TREE_BLOCK;
+}
+
+// Grid of the kernels that give a wave per job (permuted_counts,
+// partial_dependence): nb row blocks in x, and the `rounds` rounds of
+// jobs (one job per wave of a block) split over blockIdx.y until the grid
+// holds about four waves per SIMD (256 CUs x 4 SIMDs = 1024 blocks), never
+// more shares than there are rounds and within the 65535 limit of grid.y.
+static dim3 job_grid(long nb, long rounds) {
+    const long want = (1024 + nb - 1) / nb;
+    return dim3((unsigned)nb,
+                (unsigned)std::max(1L, std::min({rounds, want, 65535L})));
+}
+
+// Host checks of G stacked parameter sets (CPU tensors): mean / scale /
+// pca_mean [G, FPAD], W [G, FPAD, FPAD], cut_off [G, FPAD + 1] with
+// group-local offsets into the groups' cuts, which lie back to back in
+// `cuts`.  Returns cut_base int32 [G] (CPU), each group's first cut.
+static at::Tensor grouped_params_check(const at::Tensor& mean,
+                                       const at::Tensor& scale,
+                                       const at::Tensor& pca_mean,
+                                       const at::Tensor& W,
+                                       const at::Tensor& cuts,
+                                       const at::Tensor& cut_off, long G,
+                                       const char* op) {
+    for (const at::Tensor* p : {&mean, &scale, &pca_mean, &W})
+        TORCH_CHECK(!p->is_cuda() && p->dtype() == at::kDouble &&
+                    p->is_contiguous());
+    TORCH_CHECK(mean.numel() == G * FPAD && scale.numel() == G * FPAD &&
+                pca_mean.numel() == G * FPAD &&
+                W.numel() == G * FPAD * FPAD,
+                op, ": one parameter set per group");
+    TORCH_CHECK(!cuts.is_cuda() && cuts.dtype() == at::kFloat &&
+                cuts.is_contiguous());
+    TORCH_CHECK(!cut_off.is_cuda() && cut_off.dtype() == at::kInt &&
+                cut_off.is_contiguous() &&
+                cut_off.numel() == G * (FPAD + 1));
+    const int* co = cut_off.data_ptr<int>();
+    auto cut_base = at::empty({G}, at::kInt);
+    long n_cuts = 0;
+    for (long g = 0; g < G; ++g, co += FPAD + 1) {
+        TORCH_CHECK(co[0] == 0, op, ": cut offsets of group ", g,
+                    " must start at 0");
+        for (int f = 0; f < FPAD; ++f)
+            TORCH_CHECK(co[f + 1] >= co[f] &&
+                        co[f + 1] - co[f] <= DETECT_MAX_CUTS,
+                        op, ": bad cut count for group ", g, " feature ", f);
+        cut_base.data_ptr<int>()[g] = (int)n_cuts;
+        n_cuts += co[FPAD];
+        TORCH_CHECK(n_cuts < (1L << 31));
+    }
+    TORCH_CHECK(n_cuts == cuts.numel(), op,
+                ": cut offsets do not cover the cut array");
+    return cut_base;
+}
+
+// A checked parameter set on the device.  cuts_ptr() is null for a set
+// without cuts (data_ptr of an empty tensor is not to be relied on).
+struct DeviceParams {
+    at::Tensor mean, scale, pca_mean, W, cuts, cut_off, cut_base;
+    const float* cuts_ptr() const {
+        return cuts.numel() ? cuts.data_ptr<float>() : nullptr;
+    }
+};
+
+// cut_base may be undefined, for a kernel that serves one set.
+static DeviceParams upload_params(const at::Tensor& mean,
+                                  const at::Tensor& scale,
+                                  const at::Tensor& pca_mean,
+                                  const at::Tensor& W, const at::Tensor& cuts,
+                                  const at::Tensor& cut_off,
+                                  const at::Tensor& cut_base,
+                                  c10::Device dev) {
+    return {mean.to(dev), scale.to(dev), pca_mean.to(dev), W.to(dev),
+            cuts.to(dev), cut_off.to(dev),
+            cut_base.defined() ? cut_base.to(dev) : cut_base};
+}
+
+// ---------------------------------------------------------------------------
 // saved-detector inference (detect.hip)
 // ---------------------------------------------------------------------------
 // Parameters and cuts arrive CPU-resident: they are a few KB, and the cut
@@ -688,68 +813,35 @@ at::Tensor treeshap_paths(at::Tensor codes, at::Tensor leaf_tree,
 at::Tensor detect_encode(at::Tensor X, at::Tensor mean, at::Tensor scale,
                          at::Tensor pca_mean, at::Tensor W, bool has_pca,
                          at::Tensor cuts, at::Tensor cut_off, int64_t F) {
-    TORCH_CHECK(X.is_cuda() && X.dtype() == at::kDouble && X.dim() == 2 &&
-                X.size(1) == FPAD && X.is_contiguous());
-    TORCH_CHECK(F >= 1 && F <= FPAD);
-    for (const at::Tensor* p : {&mean, &scale, &pca_mean, &W})
-        TORCH_CHECK(!p->is_cuda() && p->dtype() == at::kDouble &&
-                    p->is_contiguous());
-    TORCH_CHECK(mean.numel() == FPAD && scale.numel() == FPAD &&
-                pca_mean.numel() == FPAD && W.numel() == FPAD * FPAD);
-    TORCH_CHECK(!cuts.is_cuda() && cuts.dtype() == at::kFloat &&
-                cuts.is_contiguous());
-    TORCH_CHECK(!cut_off.is_cuda() && cut_off.dtype() == at::kInt &&
-                cut_off.is_contiguous() && cut_off.numel() == FPAD + 1);
-    const int* co = cut_off.data_ptr<int>();
-    TORCH_CHECK(co[0] == 0, "detect_encode: cut offsets must start at 0");
-    for (int f = 0; f < FPAD; ++f)
-        TORCH_CHECK(co[f + 1] >= co[f] &&
-                    co[f + 1] - co[f] <= DETECT_MAX_CUTS,
-                    "detect_encode: bad cut count for feature ", f);
-    const int n_cuts = co[FPAD];
-    TORCH_CHECK(n_cuts == cuts.numel(),
-                "detect_encode: cut offsets do not cover the cut array");
+    const char* op = "detect_encode";
+    check_raw_rows(X, F, op);
+    grouped_params_check(mean, scale, pca_mean, W, cuts, cut_off, 1, op);
 
     const at::cuda::OptionalCUDAGuard guard(X.device());
     const long M = X.size(0);
-    TORCH_CHECK(M < (1L << 31));
     auto codes = at::empty({M, FPAD}, X.options().dtype(at::kByte));
     if (M == 0) return codes;
-    auto dev = X.device();
-    auto mean_d = mean.to(dev), scale_d = scale.to(dev);
-    auto pmean_d = pca_mean.to(dev), W_d = W.to(dev);
-    auto cuts_d = cuts.to(dev), off_d = cut_off.to(dev);
+    auto p = upload_params(mean, scale, pca_mean, W, cuts, cut_off,
+                           at::Tensor(), X.device());
     detect_encode_kernel<<<(int)((M + DETECT_BLK - 1) / DETECT_BLK),
                            DETECT_BLK, 0, current_stream()>>>(
-        X.data_ptr<double>(), mean_d.data_ptr<double>(),
-        scale_d.data_ptr<double>(), pmean_d.data_ptr<double>(),
-        W_d.data_ptr<double>(), has_pca ? 1 : 0,
-        n_cuts ? cuts_d.data_ptr<float>() : nullptr,
-        off_d.data_ptr<int>(), n_cuts, (int)M, (int)F,
+        X.data_ptr<double>(), p.mean.data_ptr<double>(),
+        p.scale.data_ptr<double>(), p.pca_mean.data_ptr<double>(),
+        p.W.data_ptr<double>(), has_pca ? 1 : 0, p.cuts_ptr(),
+        p.cut_off.data_ptr<int>(), (int)M, (int)F,
         codes.data_ptr<uint8_t>());
     return codes;
 }
 
-// (acc0, acc1) per row as float64 [M, 2].  The caller guarantees a
-// well-formed packed forest (engine/detector.py validates child ids
-// before packing); shapes are checked here.
+// (acc0, acc1) per row as float64 [M, 2].
 at::Tensor forest_proba(at::Tensor codes, at::Tensor tree_off,
                         at::Tensor nodes_packed, int64_t n_trees) {
-    TORCH_CHECK(codes.is_cuda() && codes.dtype() == at::kByte &&
-                codes.dim() == 2 && codes.size(1) == FPAD &&
-                codes.is_contiguous());
-    TORCH_CHECK(tree_off.is_cuda() && tree_off.dtype() == at::kLong &&
-                tree_off.is_contiguous() && n_trees >= 1 &&
-                tree_off.numel() == n_trees + 1);
-    TORCH_CHECK(nodes_packed.is_cuda() && nodes_packed.dtype() == at::kInt &&
-                nodes_packed.dim() == 2 && nodes_packed.size(1) == 2 &&
-                nodes_packed.is_contiguous() &&
-                nodes_packed.size(0) < (1L << 31));
+    const char* op = "forest_proba";
+    check_codes(codes, op);
+    check_forest(tree_off, nodes_packed, 1, n_trees, (1L << 31) - 1, op);
     const at::cuda::OptionalCUDAGuard guard(codes.device());
     const long M = codes.size(0);
-    TORCH_CHECK(M < (1L << 31));
-    const int n_blocks =
-        ((int)n_trees + PREDICT_TREE_BLOCK - 1) / PREDICT_TREE_BLOCK;
+    const int n_blocks = n_tree_blocks(n_trees);
     auto acc = at::empty({M, 2}, codes.options().dtype(at::kDouble));
     if (M == 0) return acc;
     auto partial = at::empty({(long)n_blocks * M, 2},
@@ -781,9 +873,7 @@ static void check_path_table(const char* op, const at::Tensor& codes,
                              const at::Tensor& elem_code,
                              const at::Tensor& elem_z, int64_t n_trees,
                              int64_t F) {
-    TORCH_CHECK(codes.is_cuda() && codes.dtype() == at::kByte &&
-                codes.dim() == 2 && codes.size(1) == FPAD &&
-                codes.is_contiguous());
+    check_codes(codes, op);
     TORCH_CHECK(F >= 1 && F <= FPAD);
     TORCH_CHECK(n_trees >= 1 && n_trees <= 65535, op,
                 ": tree count out of range");
@@ -798,7 +888,6 @@ static void check_path_table(const char* op, const at::Tensor& codes,
                 leaf_off.numel() == L + 1 && elem_code.numel() == E &&
                 L >= n_trees && L < (1L << 31) && E < (1L << 31),
                 op, ": path table sizes");
-    TORCH_CHECK(codes.size(0) < (1L << 31));
     if (codes.size(0) == 0) return;
 
     // offsets start at 0, end at the array they index and never step
@@ -945,46 +1034,46 @@ static at::Tensor holdout_block_table(const at::Tensor& seg_off, long M,
     return t.to(dev);
 }
 
-// Host checks of G stacked parameter sets (CPU tensors): mean / scale /
-// pca_mean [G, FPAD], W [G, FPAD, FPAD], cut_off [G, FPAD + 1] with
-// group-local offsets into the groups' cuts, which lie back to back in
-// `cuts`.  Returns cut_base int32 [G] (CPU), each group's first cut.
-static at::Tensor grouped_params_check(const at::Tensor& mean,
-                                       const at::Tensor& scale,
-                                       const at::Tensor& pca_mean,
-                                       const at::Tensor& W,
-                                       const at::Tensor& cuts,
-                                       const at::Tensor& cut_off, long G,
-                                       const char* op) {
-    for (const at::Tensor* p : {&mean, &scale, &pca_mean, &W})
-        TORCH_CHECK(!p->is_cuda() && p->dtype() == at::kDouble &&
-                    p->is_contiguous());
-    TORCH_CHECK(mean.numel() == G * FPAD && scale.numel() == G * FPAD &&
-                pca_mean.numel() == G * FPAD &&
-                W.numel() == G * FPAD * FPAD,
-                op, ": one parameter set per group");
-    TORCH_CHECK(!cuts.is_cuda() && cuts.dtype() == at::kFloat &&
-                cuts.is_contiguous());
-    TORCH_CHECK(!cut_off.is_cuda() && cut_off.dtype() == at::kInt &&
-                cut_off.is_contiguous() &&
-                cut_off.numel() == G * (FPAD + 1));
-    const int* co = cut_off.data_ptr<int>();
-    auto cut_base = at::empty({G}, at::kInt);
-    long n_cuts = 0;
-    for (long g = 0; g < G; ++g, co += FPAD + 1) {
-        TORCH_CHECK(co[0] == 0, op, ": cut offsets of group ", g,
-                    " must start at 0");
-        for (int f = 0; f < FPAD; ++f)
-            TORCH_CHECK(co[f + 1] >= co[f] &&
-                        co[f + 1] - co[f] <= DETECT_MAX_CUTS,
-                        op, ": bad cut count for group ", g, " feature ", f);
-        cut_base.data_ptr<int>()[g] = (int)n_cuts;
-        n_cuts += co[FPAD];
-        TORCH_CHECK(n_cuts < (1L << 31));
-    }
-    TORCH_CHECK(n_cuts == cuts.numel(), op,
-                ": cut offsets do not cover the cut array");
-    return cut_base;
+static void launch_holdout_encode(const at::Tensor& X, const at::Tensor& tab,
+                                  const DeviceParams& p, bool has_pca,
+                                  int64_t F, at::Tensor& codes,
+                                  hipStream_t s) {
+    holdout_encode_kernel<<<(int)tab.size(0), DETECT_BLK, 0, s>>>(
+        X.data_ptr<double>(), (const int4*)tab.data_ptr<int>(),
+        p.mean.data_ptr<double>(), p.scale.data_ptr<double>(),
+        p.pca_mean.data_ptr<double>(), p.W.data_ptr<double>(),
+        has_pca ? 1 : 0, p.cuts_ptr(), p.cut_off.data_ptr<int>(),
+        p.cut_base.data_ptr<int>(), (int)F, codes.data_ptr<uint8_t>());
+}
+
+static void launch_holdout_proba(const at::Tensor& codes,
+                                 const at::Tensor& tab,
+                                 const at::Tensor& tree_off,
+                                 const at::Tensor& nodes_packed,
+                                 int64_t n_trees, at::Tensor& acc,
+                                 hipStream_t s) {
+    holdout_proba_kernel<<<(int)tab.size(0), DETECT_BLK, 0, s>>>(
+        codes.data_ptr<uint8_t>(), (const int4*)tab.data_ptr<int>(),
+        tree_off.data_ptr<long>(), (const int2*)nodes_packed.data_ptr<int>(),
+        (int)n_trees, n_tree_blocks(n_trees),
+        (double2*)acc.data_ptr<double>());
+}
+
+// The unmodified rows of permuted_counts and partial_dependence, once per
+// call: (codes uint8 [M, 16], acc fp64 [M, 2]).  tab_enc and tab_acc are
+// block tables of DETECT_BLK and HOLDOUT_PROBA_ROWS rows whose x names the
+// block's detector.
+static std::pair<at::Tensor, at::Tensor> encode_and_sum(
+    const at::Tensor& X, const at::Tensor& tab_enc, const at::Tensor& tab_acc,
+    const DeviceParams& p, bool has_pca, int64_t F,
+    const at::Tensor& tree_off, const at::Tensor& nodes_packed,
+    int64_t n_trees, hipStream_t s) {
+    auto codes = at::empty({X.size(0), FPAD}, X.options().dtype(at::kByte));
+    auto acc = at::empty({X.size(0), 2}, X.options());
+    launch_holdout_encode(X, tab_enc, p, has_pca, F, codes, s);
+    launch_holdout_proba(codes, tab_acc, tree_off, nodes_packed, n_trees, acc,
+                         s);
+    return {codes, acc};
 }
 
 // detect_encode per group: rows seg_off[g]:seg_off[g+1] are encoded with
@@ -995,67 +1084,41 @@ at::Tensor holdout_encode(at::Tensor X, at::Tensor seg_off, at::Tensor mean,
                           at::Tensor scale, at::Tensor pca_mean,
                           at::Tensor W, bool has_pca, at::Tensor cuts,
                           at::Tensor cut_off, int64_t F) {
-    TORCH_CHECK(X.is_cuda() && X.dtype() == at::kDouble && X.dim() == 2 &&
-                X.size(1) == FPAD && X.is_contiguous());
-    TORCH_CHECK(F >= 1 && F <= FPAD);
+    const char* op = "holdout_encode";
+    check_raw_rows(X, F, op);
     const long M = X.size(0);
     auto dev = X.device();
-    auto tab = holdout_block_table(seg_off, M, DETECT_BLK, dev,
-                                   "holdout_encode");
+    auto tab = holdout_block_table(seg_off, M, DETECT_BLK, dev, op);
     const long G = seg_off.numel() - 1;
     auto cut_base = grouped_params_check(mean, scale, pca_mean, W, cuts,
-                                         cut_off, G, "holdout_encode");
-    const long n_cuts = cuts.numel();
+                                         cut_off, G, op);
 
     const at::cuda::OptionalCUDAGuard guard(dev);
     auto codes = at::empty({M, FPAD}, X.options().dtype(at::kByte));
     if (M == 0) return codes;
-    auto mean_d = mean.to(dev), scale_d = scale.to(dev);
-    auto pmean_d = pca_mean.to(dev), W_d = W.to(dev);
-    auto cuts_d = cuts.to(dev), off_d = cut_off.to(dev);
-    auto base_d = cut_base.to(dev);
-    holdout_encode_kernel<<<(int)tab.size(0), DETECT_BLK, 0,
-                            current_stream()>>>(
-        X.data_ptr<double>(), (const int4*)tab.data_ptr<int>(),
-        mean_d.data_ptr<double>(), scale_d.data_ptr<double>(),
-        pmean_d.data_ptr<double>(), W_d.data_ptr<double>(), has_pca ? 1 : 0,
-        n_cuts ? cuts_d.data_ptr<float>() : nullptr, off_d.data_ptr<int>(),
-        base_d.data_ptr<int>(), (int)F, codes.data_ptr<uint8_t>());
+    auto p = upload_params(mean, scale, pca_mean, W, cuts, cut_off, cut_base,
+                           dev);
+    launch_holdout_encode(X, tab, p, has_pca, F, codes, current_stream());
     return codes;
 }
 
 // forest_proba per group over one concatenated packed forest: group g
 // owns trees g * n_trees .. (g + 1) * n_trees - 1, node ids are global.
-// The caller guarantees well-formed forests, as for forest_proba.
 at::Tensor holdout_proba(at::Tensor codes, at::Tensor seg_off,
                          at::Tensor tree_off, at::Tensor nodes_packed,
                          int64_t n_trees) {
-    TORCH_CHECK(codes.is_cuda() && codes.dtype() == at::kByte &&
-                codes.dim() == 2 && codes.size(1) == FPAD &&
-                codes.is_contiguous());
+    const char* op = "holdout_proba";
+    check_codes(codes, op);
     const long M = codes.size(0);
     auto tab = holdout_block_table(seg_off, M, HOLDOUT_PROBA_ROWS,
-                                   codes.device(), "holdout_proba");
+                                   codes.device(), op);
     const long G = seg_off.numel() - 1;
-    TORCH_CHECK(tree_off.is_cuda() && tree_off.dtype() == at::kLong &&
-                tree_off.is_contiguous() && n_trees >= 1 &&
-                n_trees < (1L << 20) &&
-                tree_off.numel() == G * n_trees + 1,
-                "holdout_proba: n_trees root ids per group and an end");
-    TORCH_CHECK(nodes_packed.is_cuda() && nodes_packed.dtype() == at::kInt &&
-                nodes_packed.dim() == 2 && nodes_packed.size(1) == 2 &&
-                nodes_packed.is_contiguous() &&
-                nodes_packed.size(0) < (1L << 31));
+    check_forest(tree_off, nodes_packed, G, n_trees, MAX_GROUPED_TREES, op);
     const at::cuda::OptionalCUDAGuard guard(codes.device());
-    const int n_blocks =
-        ((int)n_trees + PREDICT_TREE_BLOCK - 1) / PREDICT_TREE_BLOCK;
     auto acc = at::empty({M, 2}, codes.options().dtype(at::kDouble));
     if (M == 0) return acc;
-    holdout_proba_kernel<<<(int)tab.size(0), DETECT_BLK, 0,
-                           current_stream()>>>(
-        codes.data_ptr<uint8_t>(), (const int4*)tab.data_ptr<int>(),
-        tree_off.data_ptr<long>(), (const int2*)nodes_packed.data_ptr<int>(),
-        (int)n_trees, n_blocks, (double2*)acc.data_ptr<double>());
+    launch_holdout_proba(codes, tab, tree_off, nodes_packed, n_trees, acc,
+                         current_stream());
     return acc;
 }
 
@@ -1067,9 +1130,7 @@ std::vector<at::Tensor> threshold_counts(at::Tensor acc, at::Tensor labels,
     TORCH_CHECK(acc.is_cuda() && acc.dtype() == at::kDouble &&
                 acc.dim() == 2 && acc.size(1) == 2 && acc.is_contiguous());
     const long M = acc.size(0);
-    TORCH_CHECK(labels.is_cuda() && labels.dtype() == at::kByte &&
-                labels.dim() == 1 && labels.is_contiguous() &&
-                labels.numel() == M);
+    check_labels(labels, M, "threshold_counts");
     TORCH_CHECK(n_trees >= 1 && n_trees < (1L << 31));
     TORCH_CHECK(!thresholds.is_cuda() && thresholds.dtype() == at::kDouble &&
                 thresholds.dim() == 1 && thresholds.is_contiguous());
@@ -1128,14 +1189,10 @@ std::vector<at::Tensor> permuted_counts(
     at::Tensor tree_off, at::Tensor nodes_packed, int64_t n_trees,
     double threshold) {
     const char* op = "permuted_counts";
-    TORCH_CHECK(X.is_cuda() && X.dtype() == at::kDouble && X.dim() == 2 &&
-                X.size(1) == FPAD && X.is_contiguous());
-    TORCH_CHECK(F >= 1 && F <= FPAD);
+    check_raw_rows(X, F, op);
     const long M = X.size(0);
     auto dev = X.device();
-    TORCH_CHECK(labels.is_cuda() && labels.dtype() == at::kByte &&
-                labels.dim() == 1 && labels.is_contiguous() &&
-                labels.numel() == M);
+    check_labels(labels, M, op);
     TORCH_CHECK(std::isfinite(threshold) || threshold < 0.0, op,
                 ": threshold must be finite (negative: argmax rule)");
     TORCH_CHECK(!seg_off.is_cuda() && seg_off.dtype() == at::kInt &&
@@ -1186,15 +1243,7 @@ std::vector<at::Tensor> permuted_counts(
     }
     TORCH_CHECK(J * R * (G + 1) * 3 < (1L << 31), op, ": too many jobs");
 
-    TORCH_CHECK(tree_off.is_cuda() && tree_off.dtype() == at::kLong &&
-                tree_off.is_contiguous() && n_trees >= 1 &&
-                n_trees < (1L << 20) &&
-                tree_off.numel() == D * n_trees + 1, op,
-                ": n_trees root ids per detector and an end");
-    TORCH_CHECK(nodes_packed.is_cuda() && nodes_packed.dtype() == at::kInt &&
-                nodes_packed.dim() == 2 && nodes_packed.size(1) == 2 &&
-                nodes_packed.is_contiguous() &&
-                nodes_packed.size(0) < (1L << 31));
+    check_forest(tree_off, nodes_packed, D, n_trees, MAX_GROUPED_TREES, op);
 
     const at::cuda::OptionalCUDAGuard guard(dev);
     auto opts = X.options().dtype(at::kInt);
@@ -1208,50 +1257,28 @@ std::vector<at::Tensor> permuted_counts(
     auto baseline = out.narrow(0, n_counts, (G + 1) * 3).view({G + 1, 3});
     if (M == 0) return {counts, baseline};
 
-    auto mean_d = mean.to(dev), scale_d = scale.to(dev);
-    auto pmean_d = pca_mean.to(dev), W_d = W.to(dev);
-    auto cuts_d = cuts.to(dev), off_d = cut_off.to(dev);
-    auto base_d = cut_base.to(dev);
+    auto p = upload_params(mean, scale, pca_mean, W, cuts, cut_off, cut_base,
+                           dev);
     auto perm_d = perm.to(dev), masks_d = masks.to(dev);
-    const float* cuts_p = cuts.numel() ? cuts_d.data_ptr<float>() : nullptr;
-    const int n_blocks =
-        ((int)n_trees + PREDICT_TREE_BLOCK - 1) / PREDICT_TREE_BLOCK;
+    auto [codes, acc] = encode_and_sum(X, tab_enc, tab_acc, p, has_pca, F,
+                                       tree_off, nodes_packed, n_trees, s);
 
-    // the unpermuted rows, once: codes and (acc0, acc1) per row
-    auto codes = at::empty({M, FPAD}, X.options().dtype(at::kByte));
-    auto acc = at::empty({M, 2}, X.options());
-    holdout_encode_kernel<<<(int)tab_enc.size(0), DETECT_BLK, 0, s>>>(
-        X.data_ptr<double>(), (const int4*)tab_enc.data_ptr<int>(),
-        mean_d.data_ptr<double>(), scale_d.data_ptr<double>(),
-        pmean_d.data_ptr<double>(), W_d.data_ptr<double>(), has_pca ? 1 : 0,
-        cuts_p, off_d.data_ptr<int>(), base_d.data_ptr<int>(), (int)F,
-        codes.data_ptr<uint8_t>());
-    holdout_proba_kernel<<<(int)tab_acc.size(0), DETECT_BLK, 0, s>>>(
-        codes.data_ptr<uint8_t>(), (const int4*)tab_acc.data_ptr<int>(),
-        tree_off.data_ptr<long>(), (const int2*)nodes_packed.data_ptr<int>(),
-        (int)n_trees, n_blocks, (double2*)acc.data_ptr<double>());
-
-    // a wave per job: split the jobs over blockIdx.y until the grid holds
-    // about four waves per SIMD (256 CUs x 4 SIMDs), and never more
-    // shares than there are rounds of IMPORTANCE_WAVES jobs
-    const long n_jobs = J * R, nb = tab.size(0);
-    const long rounds = (n_jobs + IMPORTANCE_WAVES - 1) / IMPORTANCE_WAVES;
-    const long want = (1024 + nb - 1) / nb;
-    const dim3 grid((unsigned)nb,
-                    (unsigned)std::max(1L, std::min({rounds, want, 65535L})));
+    const long n_jobs = J * R;
     auto launch = has_pca ? permuted_counts_kernel<true>
                           : permuted_counts_kernel<false>;
-    launch<<<grid, DETECT_BLK, 0, s>>>(
+    launch<<<job_grid(tab.size(0), (n_jobs + IMPORTANCE_WAVES - 1)
+                                       / IMPORTANCE_WAVES),
+             DETECT_BLK, 0, s>>>(
         X.data_ptr<double>(), labels.data_ptr<uint8_t>(),
         (const int4*)tab.data_ptr<int>(), codes.data_ptr<uint8_t>(),
         (const double2*)acc.data_ptr<double>(), perm_d.data_ptr<int>(),
-        masks_d.data_ptr<int>(), mean_d.data_ptr<double>(),
-        scale_d.data_ptr<double>(), pmean_d.data_ptr<double>(),
-        W_d.data_ptr<double>(), cuts_p, off_d.data_ptr<int>(),
-        base_d.data_ptr<int>(), (int)F, tree_off.data_ptr<long>(),
-        (const int2*)nodes_packed.data_ptr<int>(), (int)n_trees, n_blocks,
-        (int)n_jobs, (int)R, (int)M, (int)G, threshold,
-        counts.data_ptr<int>(), baseline.data_ptr<int>());
+        masks_d.data_ptr<int>(), p.mean.data_ptr<double>(),
+        p.scale.data_ptr<double>(), p.pca_mean.data_ptr<double>(),
+        p.W.data_ptr<double>(), p.cuts_ptr(), p.cut_off.data_ptr<int>(),
+        p.cut_base.data_ptr<int>(), (int)F, tree_off.data_ptr<long>(),
+        (const int2*)nodes_packed.data_ptr<int>(), (int)n_trees,
+        n_tree_blocks(n_trees), (int)n_jobs, (int)R, (int)M, (int)G,
+        threshold, counts.data_ptr<int>(), baseline.data_ptr<int>());
     return {counts, baseline};
 }
 
@@ -1276,10 +1303,7 @@ std::vector<at::Tensor> partial_dependence(
     at::Tensor tree_off, at::Tensor nodes_packed, int64_t n_trees,
     double threshold, bool want_ice) {
     const char* op = "partial_dependence";
-    TORCH_CHECK(X.is_cuda() && X.dtype() == at::kDouble && X.dim() == 2 &&
-                X.size(1) == FPAD && X.is_contiguous(), op,
-                ": X must be device float64 [M, 16]");
-    TORCH_CHECK(F >= 1 && F <= FPAD);
+    check_raw_rows(X, F, op);
     const long M = X.size(0);
     auto dev = X.device();
     TORCH_CHECK(std::isfinite(threshold) || threshold < 0.0, op,
@@ -1288,7 +1312,8 @@ std::vector<at::Tensor> partial_dependence(
                 seg_off.dim() == 1 && seg_off.numel() >= 2, op,
                 ": seg_off must be CPU int32 [G+1]");
     const long G = seg_off.numel() - 1;
-    grouped_params_check(mean, scale, pca_mean, W, cuts, cut_off, 1, op);
+    auto cut_base = grouped_params_check(mean, scale, pca_mean, W, cuts,
+                                         cut_off, 1, op);
 
     TORCH_CHECK(!job_col.is_cuda() && job_col.dtype() == at::kInt &&
                 job_col.dim() == 1 && job_col.is_contiguous(), op,
@@ -1330,14 +1355,7 @@ std::vector<at::Tensor> partial_dependence(
         TORCH_CHECK(gb[G] == tab.size(0));
     }
 
-    TORCH_CHECK(tree_off.is_cuda() && tree_off.dtype() == at::kLong &&
-                tree_off.is_contiguous() && n_trees >= 1 &&
-                n_trees < (1L << 20) && tree_off.numel() == n_trees + 1, op,
-                ": n_trees root ids and an end");
-    TORCH_CHECK(nodes_packed.is_cuda() && nodes_packed.dtype() == at::kInt &&
-                nodes_packed.dim() == 2 && nodes_packed.size(1) == 2 &&
-                nodes_packed.is_contiguous() &&
-                nodes_packed.size(0) < (1L << 31));
+    check_forest(tree_off, nodes_packed, 1, n_trees, MAX_GROUPED_TREES, op);
     TORCH_CHECK(tree_off.device() == dev && nodes_packed.device() == dev, op,
                 ": X and the forest must share a device");
 
@@ -1356,50 +1374,27 @@ std::vector<at::Tensor> partial_dependence(
     auto blk_sum = at::empty({J + 1, nb}, X.options());
     auto blk_cnt = at::empty({J + 1, nb}, X.options().dtype(at::kInt));
 
-    auto mean_d = mean.to(dev), scale_d = scale.to(dev);
-    auto pmean_d = pca_mean.to(dev), W_d = W.to(dev);
-    auto cuts_d = cuts.to(dev), off_d = cut_off.to(dev);
-    auto base_d = at::zeros({1}, at::kInt).to(dev);
+    auto p = upload_params(mean, scale, pca_mean, W, cuts, cut_off, cut_base,
+                           dev);
     auto col_d = job_col.to(dev), val_d = job_val.to(dev);
     auto grp_d = grp_blk.to(dev);
-    const float* cuts_p = cuts.numel() ? cuts_d.data_ptr<float>() : nullptr;
-    const int n_blocks =
-        ((int)n_trees + PREDICT_TREE_BLOCK - 1) / PREDICT_TREE_BLOCK;
     hipStream_t s = current_stream();
+    auto [codes, acc] = encode_and_sum(X, tab_enc, tab, p, has_pca, F,
+                                       tree_off, nodes_packed, n_trees, s);
 
-    // the unmodified rows, once: codes and (acc0, acc1) per row
-    auto codes = at::empty({M, FPAD}, X.options().dtype(at::kByte));
-    auto acc = at::empty({M, 2}, X.options());
-    holdout_encode_kernel<<<(int)tab_enc.size(0), DETECT_BLK, 0, s>>>(
-        X.data_ptr<double>(), (const int4*)tab_enc.data_ptr<int>(),
-        mean_d.data_ptr<double>(), scale_d.data_ptr<double>(),
-        pmean_d.data_ptr<double>(), W_d.data_ptr<double>(), has_pca ? 1 : 0,
-        cuts_p, off_d.data_ptr<int>(), base_d.data_ptr<int>(), (int)F,
-        codes.data_ptr<uint8_t>());
-    holdout_proba_kernel<<<(int)nb, DETECT_BLK, 0, s>>>(
-        codes.data_ptr<uint8_t>(), (const int4*)tab.data_ptr<int>(),
-        tree_off.data_ptr<long>(), (const int2*)nodes_packed.data_ptr<int>(),
-        (int)n_trees, n_blocks, (double2*)acc.data_ptr<double>());
-
-    // a wave per job: the job list is split over blockIdx.y as in
-    // permuted_counts (about 1024 blocks, never more shares than rounds of
-    // DEPENDENCE_WAVES jobs)
-    const long rounds = (J + DEPENDENCE_WAVES - 1) / DEPENDENCE_WAVES;
-    const long want = (1024 + nb - 1) / nb;
-    const dim3 grid((unsigned)nb,
-                    (unsigned)std::max(1L, std::min({rounds, want, 65535L})));
     auto launch = has_pca ? partial_dependence_kernel<true>
                           : partial_dependence_kernel<false>;
-    launch<<<grid, DETECT_BLK, 0, s>>>(
+    launch<<<job_grid(nb, (J + DEPENDENCE_WAVES - 1) / DEPENDENCE_WAVES),
+             DETECT_BLK, 0, s>>>(
         X.data_ptr<double>(), (const int4*)tab.data_ptr<int>(),
         codes.data_ptr<uint8_t>(), (const double2*)acc.data_ptr<double>(),
         col_d.data_ptr<int>(), val_d.data_ptr<double>(),
-        mean_d.data_ptr<double>(), scale_d.data_ptr<double>(),
-        pmean_d.data_ptr<double>(), W_d.data_ptr<double>(), cuts_p,
-        off_d.data_ptr<int>(), (int)F, tree_off.data_ptr<long>(),
-        (const int2*)nodes_packed.data_ptr<int>(), (int)n_trees, n_blocks,
-        (int)J, (int)M, threshold, blk_sum.data_ptr<double>(),
-        blk_cnt.data_ptr<int>(),
+        p.mean.data_ptr<double>(), p.scale.data_ptr<double>(),
+        p.pca_mean.data_ptr<double>(), p.W.data_ptr<double>(), p.cuts_ptr(),
+        p.cut_off.data_ptr<int>(), (int)F, tree_off.data_ptr<long>(),
+        (const int2*)nodes_packed.data_ptr<int>(), (int)n_trees,
+        n_tree_blocks(n_trees), (int)J, (int)M, threshold,
+        blk_sum.data_ptr<double>(), blk_cnt.data_ptr<int>(),
         want_ice ? ice.data_ptr<double>() : nullptr);
     dependence_reduce_kernel<<<(int)(J + 1), DEPENDENCE_REDUCE_BLK, 0, s>>>(
         blk_sum.data_ptr<double>(), blk_cnt.data_ptr<int>(),
@@ -1416,25 +1411,13 @@ std::vector<at::Tensor> partial_dependence(
 at::Tensor forest_leaves(at::Tensor codes, at::Tensor tree_off,
                          at::Tensor nodes_packed, int64_t n_trees) {
     const char* op = "forest_leaves";
-    TORCH_CHECK(codes.is_cuda() && codes.dtype() == at::kByte &&
-                codes.dim() == 2 && codes.size(1) == FPAD &&
-                codes.is_contiguous(), op,
-                ": codes must be device uint8 [M, 16]");
-    TORCH_CHECK(tree_off.is_cuda() && tree_off.dtype() == at::kLong &&
-                tree_off.is_contiguous() && n_trees >= 1 &&
-                n_trees <= PROX_MAX_T && tree_off.numel() == n_trees + 1,
-                op, ": n_trees root ids and an end");
-    TORCH_CHECK(nodes_packed.is_cuda() && nodes_packed.dtype() == at::kInt &&
-                nodes_packed.dim() == 2 && nodes_packed.size(1) == 2 &&
-                nodes_packed.is_contiguous() &&
-                nodes_packed.size(0) < (1L << 31), op,
-                ": nodes must be device int32 [n_nodes, 2]");
+    check_codes(codes, op);
+    check_forest(tree_off, nodes_packed, 1, n_trees, PROX_MAX_T, op);
     TORCH_CHECK(codes.device() == tree_off.device() &&
                 codes.device() == nodes_packed.device(), op,
                 ": tensors on different devices");
     const at::cuda::OptionalCUDAGuard guard(codes.device());
     const long M = codes.size(0);
-    TORCH_CHECK(M < (1L << 31));
     auto leaf = at::empty({M, n_trees}, codes.options().dtype(at::kInt));
     if (M == 0) return leaf;
     const long total = M * n_trees;

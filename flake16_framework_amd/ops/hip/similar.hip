@@ -1,6 +1,6 @@
 // Forest proximity for a saved detector (engine/similar.py), gfx950.
 //
-//   forest_leaves_kernel    the walk of forest_proba_partial_kernel, one
+//   forest_leaves_kernel    the tree walk of detector_steps.h, one
 //                           thread per (row, tree); writes the tree-local
 //                           canonical id of the leaf reached
 //   prox_wide_kernel        raises a flag if an id does not fit 16 bits
@@ -38,7 +38,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "detect.hip"
+#include "detector_steps.h"
 
 #define PROX_BLK 256      // lanes = queries per workgroup
 #define PROX_D 52         // dwords of a row compared per piece (registers)
@@ -51,28 +51,16 @@
 __global__ __launch_bounds__(DETECT_BLK) void forest_leaves_kernel(
     const uint8_t* __restrict__ codes,     // [M, FPAD]
     const long* __restrict__ tree_off,     // [T + 1] root ids
-    const int2* __restrict__ nodes,        // packed records (detect.hip)
+    const int2* __restrict__ nodes,        // packed records
     int M, int n_trees,
     int* __restrict__ leaf /* [M, T] */) {
     const long idx = (long)blockIdx.x * DETECT_BLK + threadIdx.x;
     if (idx >= (long)M * n_trees) return;
     const int row = (int)(idx % M);
     const int t = (int)(idx / M);
-
-    const uint4 cw = *(const uint4*)(codes + (size_t)row * FPAD);
-    const uint64_t c_lo = (uint64_t)cw.x | ((uint64_t)cw.y << 32);
-    const uint64_t c_hi = (uint64_t)cw.z | ((uint64_t)cw.w << 32);
-
     const int root = (int)tree_off[t];
-    int id = root;
-    int2 nd = nodes[id];
-    while (nd.x < 0) {
-        const int f = nd.y & 0xFF;
-        const int code =
-            (int)(((f & 8 ? c_hi : c_lo) >> ((f & 7) * 8)) & 0xFF);
-        id = (nd.x & 0x7FFFFFFF) + (code > (nd.y >> 8));
-        nd = nodes[id];
-    }
+    int id;
+    tree_leaf(nodes, root, load_codes(codes, row), id);
     leaf[(size_t)row * n_trees + t] = id - root;
 }
 

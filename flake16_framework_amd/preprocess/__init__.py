@@ -61,7 +61,7 @@ def apply_preprocessing(X, spec):
 # detector (engine/detector.py) has to apply the SAME transform to tests it
 # has never seen, so the fit is kept.  The fit always runs here, on the host
 # in fp64, for both backends.  The transform's arithmetic order is pinned so
-# the device kernel (ops/hip/detect.hip) reproduces it bit for bit.
+# the device kernels (ops/hip/detector_steps.h) reproduce it bit for bit.
 # ---------------------------------------------------------------------------
 def fit_preprocessing(X, spec):
     """Fit `spec` (None | 'scale' | 'scale+pca') on X.

@@ -34,6 +34,7 @@ setup(
                      "flake16_framework_amd/ops/hip/importance.hip",
                      "flake16_framework_amd/ops/hip/dependence.hip",
                      "flake16_framework_amd/ops/hip/similar.hip",
+                     "flake16_framework_amd/ops/hip/detector_steps.h",
                      "flake16_framework_amd/ops/hip/philox.h",
                      "flake16_framework_amd/ops/hip/wave_ops.h"],
             extra_compile_args={

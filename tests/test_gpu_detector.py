@@ -244,3 +244,108 @@ def test_fit_equal_across_backends(keys, train_tests, other_tests):
     assert len(got["proba"]) == 257
     np.testing.assert_array_equal(got["proba"], want["proba"])
     np.testing.assert_array_equal(got["pred"], want["pred"])
+
+
+@pytest.mark.parametrize("spec", [None, "scale+pca"])
+def test_ops_agree_on_one_input(spec):
+    """The ops that share the encode, tree-walk and rule steps, pinned to
+    each other on one input: 130 rows (two 64-row blocks and a tail of 2)
+    in three groups of 64, 0 and 66 rows, F = 7, 11 trees (two tree blocks,
+    the second short).  Every group is served by a copy of one detector;
+    a different detector stands in front of the three copies in the stacked
+    arrays, so every row that matters is reached through non-zero
+    parameter, cut and root offsets.  The grouped encode and sums take one
+    group per stacked detector, so there the dummy owns a leading group
+    without rows."""
+    from flake16_framework_amd.engine.dependence import partial_dependence
+    from flake16_framework_amd.engine.detector import device_inputs
+    from flake16_framework_amd.engine.holdout import (
+        grouped_acc, grouped_inputs,
+    )
+    from flake16_framework_amd.engine.importance import permuted_counts
+    from flake16_framework_amd.ops.backend import get_ops
+    ops = get_ops()
+    F, n_trees, M = 7, 11, 130
+    det, X, _ = _hand_built(F, spec, n_trees, seed=31)
+    dummy, _, _ = _hand_built(F, spec, n_trees, seed=32)
+    assert not np.array_equal(dummy.cuts[:8], det.cuts[:8])
+    X = X[:M]
+    i32 = lambda v: torch.from_numpy(np.asarray(v, dtype=np.int32))
+    seg3, seg4 = [0, 64, 64, M], [0, 0, 64, 64, M]
+
+    one = device_inputs(det, X)
+    stacked = grouped_inputs([dummy, det, det, det], X, seg4)
+    dev = one["X64"].device
+
+    # encode and sums: single detector against the grouped kernels
+    codes = ops.detect_encode(one["X64"], one["mean"], one["scale"],
+                              one["pca_mean"], one["W"], one["has_pca"],
+                              one["cuts"], one["cut_off"], F)
+    g_codes = ops.holdout_encode(
+        stacked["X64"], stacked["seg_off"], stacked["mean"],
+        stacked["scale"], stacked["pca_mean"], stacked["W"],
+        stacked["has_pca"], stacked["cuts"], stacked["cut_off"], F)
+    assert torch.equal(codes, g_codes)
+    assert len(torch.unique(codes, dim=0)) > M // 2
+    acc = ops.forest_proba(codes, one["tree_off"], one["nodes"], n_trees)
+    assert torch.equal(acc, grouped_acc(ops, stacked))
+    acc_np = acc.cpu().numpy()
+    assert len(np.unique(acc_np[:, 1])) > 10
+
+    # ICE: a job that writes row 0's own value back leaves its acc1 alone
+    grouped_one = grouped_inputs([det], X, seg3)
+    _, _, ice = partial_dependence(
+        ops, grouped_one, i32(range(F)),
+        torch.from_numpy(np.ascontiguousarray(X[0], dtype=np.float64)),
+        want_ice=True)
+    np.testing.assert_array_equal(ice[:, 0].cpu().numpy(),
+                                  np.full(F, acc_np[0, 1]))
+
+    # ICE of a job that does change codes: another row's value in the
+    # 255-cut column, against encode + sums of the explicitly edited rows
+    X_edit = X.copy()
+    X_edit[:, MANY_CUTS] = X[77, MANY_CUTS]
+    edited = device_inputs(det, X_edit)
+    codes_edit = ops.detect_encode(
+        edited["X64"], one["mean"], one["scale"], one["pca_mean"], one["W"],
+        one["has_pca"], one["cuts"], one["cut_off"], F)
+    assert int((codes_edit != codes).any(dim=1).sum()) > M // 2
+    acc_edit = ops.forest_proba(codes_edit, one["tree_off"], one["nodes"],
+                                n_trees)
+    assert not torch.equal(acc_edit, acc)
+    _, _, ice = partial_dependence(
+        ops, grouped_one, i32([MANY_CUTS]),
+        torch.tensor([X[77, MANY_CUTS]], dtype=torch.float64),
+        want_ice=True)
+    assert torch.equal(ice[0], acc_edit[:, 1])
+
+    # the identity permutation changes nothing, whatever the mask
+    labels = torch.from_numpy(
+        np.random.RandomState(5).randint(0, 2, size=M).astype(np.uint8)
+    ).to(dev)
+    assert 0 < int(labels.sum()) < M
+    threshold = 0.5
+    curve, argmax = ops.threshold_counts(
+        acc, labels, i32(seg3), n_trees, torch.tensor([threshold],
+                                                      dtype=torch.float64))
+    three = dict(stacked, seg_off=i32(seg3))
+    for thr, want in ((None, argmax), (threshold, curve[:, 0])):
+        counts, baseline = permuted_counts(
+            ops, three, labels, i32([1, 2, 3]), i32(np.arange(M)[None]),
+            i32([1, 1 << (F - 1), (1 << F) - 1]), thr)
+        assert int(want.sum()) > 0
+        assert torch.equal(baseline, want)
+        for j in range(3):
+            assert torch.equal(counts[j, 0], baseline)
+
+    # leaves: each tree's leaf record gives the term forest_proba sums
+    leaves = ops.forest_leaves(codes, one["tree_off"], one["nodes"],
+                               n_trees).cpu().numpy()
+    nodes = one["nodes"].cpu().numpy()
+    for t in range(n_trees):
+        rec = nodes[det.tree_off[t] + leaves[:, t]]
+        assert (rec[:, 0] >= 0).all()                   # leaves, not splits
+        c = rec.view(np.float32).astype(np.float64)
+        term = ops.forest_proba(codes, one["tree_off"][t:t + 2],
+                                one["nodes"], 1).cpu().numpy()
+        np.testing.assert_array_equal(term, c / c.sum(axis=1, keepdims=True))
