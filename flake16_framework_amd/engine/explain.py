@@ -18,8 +18,8 @@ Conventions
 The algorithm is path-dependent TreeSHAP over MERGED leaf paths
 (models/mergedpaths.py): at most 16 elements per path, no UNWIND along it.
 
-Pinned arithmetic (the contract ops/hip/explain.hip reproduces bit for
-bit; fp64, no fused multiply-add, every expression left to right):
+Pinned arithmetic (the contract ops/hip/detector_shap.hip reproduces bit
+for bit; fp64, no fused multiply-add, every expression left to right):
   per (leaf, row)
     start from the sentinel (w[0] = 1), EXTEND with each element in table
     order, o in {0.0, 1.0} from the interval test, as treeshap_ref._extend:
@@ -40,6 +40,7 @@ bit; fp64, no fused multiply-add, every expression left to right):
 """
 
 import json
+from typing import NamedTuple
 
 import numpy as np
 
@@ -139,7 +140,7 @@ def shap_ref(detector, paths, codes):
 
 
 def pack_elements(paths):
-    """int32 [E] element records (layout: ops/hip/explain.hip)."""
+    """int32 [E] element records (layout: ops/hip/detector_shap.hip)."""
     return (paths.feature.astype(np.int32)
             | ((paths.lo.astype(np.int32) + 1) << 8)
             | (paths.hi.astype(np.int32) << 20))
@@ -179,19 +180,37 @@ def explain_device(ops, detector, paths, X):
     return codes, table, acc, phi
 
 
+class Explained(NamedTuple):
+    """explain()'s result and what interact goes on from.  codes and phi
+    are what the backend computed with: device tensors (phi [M, 16]) with
+    the device path table for hip, host arrays (phi [M, F]) and no table
+    for ref.  Without a test all three are None."""
+    res: dict
+    backend: str
+    paths: object
+    codes: object = None
+    table: object = None
+    phi: object = None
+
+
 def _explain_hip(detector, paths, X):
+    """(acc0, acc1, phi [M, F]) on the host, then the resident codes,
+    table and phi [M, 16]."""
     from ..ops.backend import get_ops
 
-    _, _, acc, phi = explain_device(get_ops(), detector, paths, X)
-    acc = acc.cpu().numpy()
-    return acc[:, 0], acc[:, 1], phi.cpu().numpy()[:, :detector.n_features]
+    codes, table, acc, phi = explain_device(get_ops(), detector, paths, X)
+    acc, phi_host = acc.cpu().numpy(), phi.cpu().numpy()
+    return (acc[:, 0], acc[:, 1], phi_host[:, :detector.n_features],
+            codes, table, phi)
 
 
 def _explain_ref(detector, paths, X):
+    """(acc0, acc1, phi [M, F]), then the codes, no table and phi again."""
     T = transform_preprocessing(X, detector.preprocessing_params())
     codes = bin_codes(T.astype(np.float32), detector.cut_list())
     acc0, acc1 = accumulate_proba(detector.trees(), codes)
-    return acc0, acc1, shap_ref(detector, paths, codes)
+    phi = shap_ref(detector, paths, codes)
+    return acc0, acc1, phi, codes, None, phi
 
 
 def input_rows(detector, tests=None, tests_file=None):
@@ -205,28 +224,34 @@ def input_rows(detector, tests=None, tests_file=None):
     return np.zeros((0, detector.n_features)), none, none
 
 
-def explain(detector, tests=None, tests_file=None, backend="auto"):
-    """detect() plus attributions for every test of a tests.json.
-
-    Returns detect's "proba", "pred", "projects", "nodeids" and
-    "phi" float64 [M, F], "base_value" float, "feature_names" tuple."""
+def explain_more(detector, tests, tests_file, backend):
+    """explain() as an Explained."""
     backend = _resolve_backend(backend)
     detector.validate()
     paths = build_merged_paths(detector)
     X, projects, nodeids = input_rows(detector, tests, tests_file)
     if len(X) == 0:
         acc0 = acc1 = np.zeros(0)
-        phi = np.zeros((0, detector.n_features))
+        phi, used = np.zeros((0, detector.n_features)), ()
     elif backend == "hip":
-        acc0, acc1, phi = _explain_hip(detector, paths, X)
+        acc0, acc1, phi, *used = _explain_hip(detector, paths, X)
     else:
-        acc0, acc1, phi = _explain_ref(detector, paths, X)
-    return {"proba": acc1 / detector.n_trees,
-            "pred": (acc1 > acc0).astype(np.uint8),
-            "projects": projects, "nodeids": nodeids,
-            "phi": np.ascontiguousarray(phi, dtype=np.float64),
-            "base_value": base_value(detector, paths),
-            "feature_names": feature_names(detector)}
+        acc0, acc1, phi, *used = _explain_ref(detector, paths, X)
+    res = {"proba": acc1 / detector.n_trees,
+           "pred": (acc1 > acc0).astype(np.uint8),
+           "projects": projects, "nodeids": nodeids,
+           "phi": np.ascontiguousarray(phi, dtype=np.float64),
+           "base_value": base_value(detector, paths),
+           "feature_names": feature_names(detector)}
+    return Explained(res, backend, paths, *used)
+
+
+def explain(detector, tests=None, tests_file=None, backend="auto"):
+    """detect() plus attributions for every test of a tests.json.
+
+    Returns detect's "proba", "pred", "projects", "nodeids" and
+    "phi" float64 [M, F], "base_value" float, "feature_names" tuple."""
+    return explain_more(detector, tests, tests_file, backend).res
 
 
 def write_explanations(detector, tests=None, tests_file=None,

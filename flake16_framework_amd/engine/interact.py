@@ -18,8 +18,8 @@ base_value + sum_{g, f} Phi[g, f] == proba up to rounding.
 A feature appears at most once in a merged leaf path
 (models/mergedpaths.py), so conditioning on g is dropping its element.
 
-Pinned arithmetic (the contract ops/hip/interact.hip reproduces bit for
-bit; fp64, no fused multiply-add, every expression left to right):
+Pinned arithmetic (the contract ops/hip/detector_shap.hip reproduces bit
+for bit; fp64, no fused multiply-add, every expression left to right):
   per leaf with elements e_0..e_{n-1} and value v, per element c with
   feature g
     the reduced path is the same elements in table order without c; on it
@@ -45,15 +45,7 @@ import json
 import numpy as np
 
 from ..constants import INTERACTIONS_FILE
-from ..models.binning import bin_codes
-from ..models.forest_ref import accumulate_proba
-from ..models.mergedpaths import build_merged_paths
-from ..preprocess import transform_preprocessing
-from .detector import _resolve_backend
-from .explain import (
-    _blocked_tree_sum, _leaf_terms, base_value, explain_device,
-    feature_names, input_rows, shap_ref,
-)
+from .explain import _blocked_tree_sum, _leaf_terms, explain_more
 
 
 def interactions_ref(detector, paths, codes, phi):
@@ -96,51 +88,26 @@ def device_interactions(ops, codes, table, phi, n_trees, F):
         table["elem_code"], table["elem_z"], phi, n_trees, F)
 
 
-def _interact_hip(detector, paths, X):
-    from ..ops.backend import get_ops
-
-    ops = get_ops()
-    F = detector.n_features
-    codes, table, acc, phi = explain_device(ops, detector, paths, X)
-    inter = device_interactions(ops, codes, table, phi, detector.n_trees, F)
-    acc = acc.cpu().numpy()
-    return (acc[:, 0], acc[:, 1], phi.cpu().numpy()[:, :F],
-            inter.cpu().numpy()[:, :F, :F])
-
-
-def _interact_ref(detector, paths, X):
-    T = transform_preprocessing(X, detector.preprocessing_params())
-    codes = bin_codes(T.astype(np.float32), detector.cut_list())
-    acc0, acc1 = accumulate_proba(detector.trees(), codes)
-    phi = shap_ref(detector, paths, codes)
-    return acc0, acc1, phi, interactions_ref(detector, paths, codes, phi)
-
-
 def interact(detector, tests=None, tests_file=None, backend="auto"):
     """explain() plus interaction values for every test of a tests.json.
 
     Returns explain's fields unchanged ("proba", "pred", "projects",
     "nodeids", "phi", "base_value", "feature_names") and "interactions",
     float64 [M, F, F]."""
-    backend = _resolve_backend(backend)
-    detector.validate()
-    paths = build_merged_paths(detector)
-    X, projects, nodeids = input_rows(detector, tests, tests_file)
+    ex = explain_more(detector, tests, tests_file, backend)
     F = detector.n_features
-    if len(X) == 0:
-        acc0 = acc1 = np.zeros(0)
-        phi, inter = np.zeros((0, F)), np.zeros((0, F, F))
-    elif backend == "hip":
-        acc0, acc1, phi, inter = _interact_hip(detector, paths, X)
+    if len(ex.res["proba"]) == 0:
+        inter = np.zeros((0, F, F))
+    elif ex.backend == "hip":
+        from ..ops.backend import get_ops
+
+        inter = device_interactions(get_ops(), ex.codes, ex.table, ex.phi,
+                                    detector.n_trees, F)
+        inter = inter.cpu().numpy()[:, :F, :F]
     else:
-        acc0, acc1, phi, inter = _interact_ref(detector, paths, X)
-    return {"proba": acc1 / detector.n_trees,
-            "pred": (acc1 > acc0).astype(np.uint8),
-            "projects": projects, "nodeids": nodeids,
-            "phi": np.ascontiguousarray(phi, dtype=np.float64),
-            "base_value": base_value(detector, paths),
-            "feature_names": feature_names(detector),
-            "interactions": np.ascontiguousarray(inter, dtype=np.float64)}
+        inter = interactions_ref(detector, ex.paths, ex.codes, ex.phi)
+    return dict(ex.res,
+                interactions=np.ascontiguousarray(inter, dtype=np.float64))
 
 
 def pair_index(F):

@@ -18,7 +18,7 @@ the tree depth, and the merged element is the same for every row:
 Elements are listed in order of first appearance on the path.  The table is
 a CSR over all leaves of all trees: trees in order, leaves in ascending
 canonical node id within a tree.  engine/explain.py holds the arithmetic
-that consumes it (numpy) and ops/hip/explain.hip the kernel.
+that consumes it (numpy) and ops/hip/detector_shap.hip the kernel.
 """
 
 from dataclasses import dataclass

@@ -14,8 +14,7 @@
 #include "scaler_pca.hip"
 #include "treeshap.hip"
 #include "detect.hip"
-#include "explain.hip"
-#include "interact.hip"
+#include "detector_shap.hip"
 #include "holdout.hip"
 #include "importance.hip"
 #include "dependence.hip"
@@ -861,7 +860,7 @@ at::Tensor forest_proba(at::Tensor codes, at::Tensor tree_off,
 }
 
 // ---------------------------------------------------------------------------
-// saved-detector TreeSHAP (explain.hip)
+// saved-detector TreeSHAP and SHAP interaction values (detector_shap.hip)
 // ---------------------------------------------------------------------------
 // The checks the ops over the merged-path table share: shapes and dtypes
 // on the host, then (when there are rows) everything a kernel indexes
@@ -904,6 +903,43 @@ static void check_path_table(const char* op, const at::Tensor& codes,
     TORCH_CHECK(ok.item<bool>(), op, ": malformed path table");
 }
 
+// What the two ops over the table share past the checks: the workspace
+// partial [T, G, FPAD, rows] (G = F slots g when PAIRS, else 1) bounded at
+// 256 MiB, so rows go in chunks; per chunk the tree kernel, then
+// combine(partial, row0, rows of the chunk, gx, stream), the op's own
+// launch.  An empty element table is passed as null pointers.
+template <bool PAIRS, typename Combine>
+static void shap_row_chunks(const at::Tensor& codes,
+                            const at::Tensor& tree_leaf_off,
+                            const at::Tensor& leaf_off,
+                            const at::Tensor& leaf_val,
+                            const at::Tensor& elem_code,
+                            const at::Tensor& elem_z, int64_t n_trees,
+                            int64_t F, Combine combine) {
+    const long M = codes.size(0), E = elem_z.numel();
+    const long G = PAIRS ? F : 1;
+    const long ws_cap = 256L << 20;
+    const long per_row = n_trees * G * FPAD * (long)sizeof(double);
+    long chunk = std::max<long>(EXPLAIN_BLK,
+                                ws_cap / per_row / EXPLAIN_BLK * EXPLAIN_BLK);
+    chunk = std::min(chunk, M);
+    auto partial = at::empty({n_trees * G * FPAD * chunk},
+                             codes.options().dtype(at::kDouble));
+    hipStream_t s = current_stream();
+    for (long row0 = 0; row0 < M; row0 += chunk) {
+        const int mc = (int)std::min(chunk, M - row0);
+        const int gx = (mc + EXPLAIN_BLK - 1) / EXPLAIN_BLK;
+        detector_shap_tree_kernel<PAIRS>
+            <<<dim3(gx, (int)n_trees, (int)G), EXPLAIN_BLK, 0, s>>>(
+                codes.data_ptr<uint8_t>(), tree_leaf_off.data_ptr<int>(),
+                leaf_off.data_ptr<int>(), leaf_val.data_ptr<double>(),
+                E ? elem_code.data_ptr<int>() : nullptr,
+                E ? elem_z.data_ptr<double>() : nullptr, (int)row0, mc,
+                partial.data_ptr<double>());
+        combine(partial.data_ptr<double>(), (int)row0, mc, gx, s);
+    }
+}
+
 // Class-1 attributions as float64 [M, FPAD] (columns >= F are zero) from
 // the codes of detect_encode and the merged-path table of
 // models/mergedpaths.py, all device-resident.
@@ -913,41 +949,22 @@ at::Tensor detector_shap(at::Tensor codes, at::Tensor tree_leaf_off,
                          int64_t n_trees, int64_t F) {
     check_path_table("detector_shap", codes, tree_leaf_off, leaf_off,
                      leaf_val, elem_code, elem_z, n_trees, F);
-    const long M = codes.size(0), E = elem_z.numel();
+    const long M = codes.size(0);
 
     const at::cuda::OptionalCUDAGuard guard(codes.device());
     auto phi = at::empty({M, FPAD}, codes.options().dtype(at::kDouble));
     if (M == 0) return phi;
-
-    // workspace [T, FPAD, rows] bounded at 256 MiB: rows go in chunks
-    const long ws_cap = 256L << 20;
-    const long per_row = n_trees * FPAD * (long)sizeof(double);
-    long chunk = std::max<long>(EXPLAIN_BLK,
-                                ws_cap / per_row / EXPLAIN_BLK * EXPLAIN_BLK);
-    chunk = std::min(chunk, M);
-    auto partial = at::empty({n_trees * FPAD * chunk},
-                             codes.options().dtype(at::kDouble));
-    hipStream_t s = current_stream();
-    for (long row0 = 0; row0 < M; row0 += chunk) {
-        const int mc = (int)std::min(chunk, M - row0);
-        const int gx = (mc + EXPLAIN_BLK - 1) / EXPLAIN_BLK;
-        detector_shap_tree_kernel<<<dim3(gx, (int)n_trees), EXPLAIN_BLK, 0,
-                                    s>>>(
-            codes.data_ptr<uint8_t>(), tree_leaf_off.data_ptr<int>(),
-            leaf_off.data_ptr<int>(), leaf_val.data_ptr<double>(),
-            E ? elem_code.data_ptr<int>() : nullptr,
-            E ? elem_z.data_ptr<double>() : nullptr, (int)row0, mc,
-            partial.data_ptr<double>());
-        detector_shap_combine_kernel<<<dim3(gx, FPAD), EXPLAIN_BLK, 0, s>>>(
-            partial.data_ptr<double>(), (int)row0, mc, (int)n_trees,
-            phi.data_ptr<double>());
-    }
+    shap_row_chunks<false>(
+        codes, tree_leaf_off, leaf_off, leaf_val, elem_code, elem_z, n_trees,
+        F, [&](const double* partial, int row0, int mc, int gx,
+               hipStream_t s) {
+            detector_shap_combine_kernel<<<dim3(gx, FPAD), EXPLAIN_BLK, 0,
+                                           s>>>(
+                partial, row0, mc, (int)n_trees, phi.data_ptr<double>());
+        });
     return phi;
 }
 
-// ---------------------------------------------------------------------------
-// saved-detector SHAP interaction values (interact.hip)
-// ---------------------------------------------------------------------------
 // Class-1 interaction values as float64 [M, FPAD, FPAD] (rows and columns
 // >= F are zero) from the inputs of detector_shap and its output phi.
 at::Tensor detector_shap_interactions(
@@ -956,7 +973,7 @@ at::Tensor detector_shap_interactions(
     at::Tensor phi, int64_t n_trees, int64_t F) {
     check_path_table("detector_shap_interactions", codes, tree_leaf_off,
                      leaf_off, leaf_val, elem_code, elem_z, n_trees, F);
-    const long M = codes.size(0), E = elem_z.numel();
+    const long M = codes.size(0);
     TORCH_CHECK(phi.is_cuda() && phi.device() == codes.device() &&
                 phi.dtype() == at::kDouble && phi.dim() == 2 &&
                 phi.size(0) == M && phi.size(1) == FPAD &&
@@ -967,31 +984,15 @@ at::Tensor detector_shap_interactions(
     const at::cuda::OptionalCUDAGuard guard(codes.device());
     auto out = at::zeros({M, FPAD, FPAD}, codes.options().dtype(at::kDouble));
     if (M == 0) return out;
-
-    // workspace [T, F, FPAD, rows] bounded at 256 MiB: rows go in chunks
-    const long ws_cap = 256L << 20;
-    const long per_row = n_trees * F * FPAD * (long)sizeof(double);
-    long chunk = std::max<long>(EXPLAIN_BLK,
-                                ws_cap / per_row / EXPLAIN_BLK * EXPLAIN_BLK);
-    chunk = std::min(chunk, M);
-    auto partial = at::empty({n_trees * F * FPAD * chunk},
-                             codes.options().dtype(at::kDouble));
-    hipStream_t s = current_stream();
-    for (long row0 = 0; row0 < M; row0 += chunk) {
-        const int mc = (int)std::min(chunk, M - row0);
-        const int gx = (mc + EXPLAIN_BLK - 1) / EXPLAIN_BLK;
-        detector_interact_tree_kernel<<<dim3(gx, (int)n_trees, (int)F),
-                                        EXPLAIN_BLK, 0, s>>>(
-            codes.data_ptr<uint8_t>(), tree_leaf_off.data_ptr<int>(),
-            leaf_off.data_ptr<int>(), leaf_val.data_ptr<double>(),
-            E ? elem_code.data_ptr<int>() : nullptr,
-            E ? elem_z.data_ptr<double>() : nullptr, (int)row0, mc,
-            partial.data_ptr<double>());
-        detector_interact_combine_kernel<<<dim3(gx, (int)F), EXPLAIN_BLK, 0,
-                                           s>>>(
-            partial.data_ptr<double>(), phi.data_ptr<double>(), (int)row0,
-            mc, (int)n_trees, out.data_ptr<double>());
-    }
+    shap_row_chunks<true>(
+        codes, tree_leaf_off, leaf_off, leaf_val, elem_code, elem_z, n_trees,
+        F, [&](const double* partial, int row0, int mc, int gx,
+               hipStream_t s) {
+            detector_interact_combine_kernel<<<dim3(gx, (int)F), EXPLAIN_BLK,
+                                               0, s>>>(
+                partial, phi.data_ptr<double>(), row0, mc, (int)n_trees,
+                out.data_ptr<double>());
+        });
     return out;
 }
 

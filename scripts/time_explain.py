@@ -5,7 +5,7 @@ A detector is fitted on synthetic tests (seed 0) and the rows of a second
 synthetic file (seed 1) are encoded once; on those resident codes, after a
 warm-up of both, device events time alternately
 
-  merged   detector_shap (ops/hip/explain.hip) over the merged-path table
+  merged   detector_shap (ops/hip/detector_shap.hip) over the merged-path table
   paths    treeshap_paths (ops/hip/treeshap.hip) over the same trees'
            root->leaf node paths
 

@@ -5,8 +5,8 @@ A detector is fitted on synthetic tests (seed 0) and the rows of a second
 synthetic file (seed 1) are encoded once; on those resident codes, after a
 warm-up of both, device events time alternately
 
-  interact  detector_shap_interactions (ops/hip/interact.hip), given phi
-  shap      detector_shap (ops/hip/explain.hip) on the same rows
+  interact  detector_shap_interactions (ops/hip/detector_shap.hip), given phi
+  shap      detector_shap (the same file and tree kernel) on the same rows
 
 (median, min and max over --reps).  The op count predicts a ratio of about
 the mean number of elements per leaf: every leaf is visited once per

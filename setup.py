@@ -28,8 +28,7 @@ setup(
                      "flake16_framework_amd/ops/hip/scaler_pca.hip",
                      "flake16_framework_amd/ops/hip/treeshap.hip",
                      "flake16_framework_amd/ops/hip/detect.hip",
-                     "flake16_framework_amd/ops/hip/explain.hip",
-                     "flake16_framework_amd/ops/hip/interact.hip",
+                     "flake16_framework_amd/ops/hip/detector_shap.hip",
                      "flake16_framework_amd/ops/hip/holdout.hip",
                      "flake16_framework_amd/ops/hip/importance.hip",
                      "flake16_framework_amd/ops/hip/dependence.hip",

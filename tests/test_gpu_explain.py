@@ -1,4 +1,4 @@
-"""GPU tests for explain: the explain.hip kernels against the numpy
+"""GPU tests for explain: the detector_shap.hip kernels against the numpy
 reference bit for bit on hand-built detectors (consistent counts, 16-element
 paths, interval edges), and on hip-fitted detectors."""
 

@@ -1,4 +1,4 @@
-"""GPU tests for interact: the interact.hip kernels against the numpy
+"""GPU tests for interact: the detector_shap.hip kernels against the numpy
 reference bit for bit on the hand-built detectors of test_gpu_explain
 (16-element leaves, root leaves, a chain, rows on interval edges) and on
 hip-fitted detectors."""
@@ -133,6 +133,25 @@ def test_rows_in_two_chunks():
     tests = _as_tests(X, big.feature_cols, M_POOL)
     want = interact(big, tests=tests, backend="ref")
     _assert_same(interact(big, tests=tests, backend="hip"), want)
+    tail = want["interactions"][255:].reshape(2, -1)
+    assert np.ptp(tail, axis=0).max() > 0       # rows 255, 256 differ
+
+
+def test_rows_in_two_chunks_below_the_padded_width():
+    """As test_rows_in_two_chunks with F = 7: the workspace is
+    [T, 7, 16, rows] and the grid has 7 slots g, so neither equals the
+    padded 16.  1024 trees make a chunk 256 rows again."""
+    from flake16_framework_amd.engine.interact import interact
+    n_trees, F = 1024, 7
+    assert (256 << 20) // (n_trees * F * 16 * 8) // 256 * 256 == 256
+    det, X, _ = _hand_built(F, None, 23, seed=79)
+    rng = np.random.RandomState(80)
+    trees = det.trees() + [_tree(_leaf(rng)) for _ in range(n_trees - 23)]
+    big = _root_leaf_forest(det, trees, n_trees)
+    tests = _as_tests(X, big.feature_cols, M_POOL)
+    want = interact(big, tests=tests, backend="ref")
+    _assert_same(interact(big, tests=tests, backend="hip"), want)
+    assert want["interactions"].shape == (257, F, F)
     tail = want["interactions"][255:].reshape(2, -1)
     assert np.ptp(tail, axis=0).max() > 0       # rows 255, 256 differ
 
